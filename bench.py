@@ -20,6 +20,10 @@ ranks; a WORLD_SIZE that disagrees with ``--gpus`` is an error.  ``--allreduce-g
 seven CrissCrossAttention parameter gradients (328,321 floats, what DDP moves for this module: engine.py:75) to
 every step.
 
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0's y, A, dq, dk, dv, dgamma) as ``DIR/<name>.npy``
+in float32, a fixed, seeded sample of the elements of any output above 2^20 of them (under 64 MB in all).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
 Rank 0 prints ONE JSON line: the driver contract plus
   ``roofline``      op-level: SURVEY 8(d) algorithmic bytes of one step / the step time, against 8 TB/s; the
                     slowest single launch is described under ``roofline.dominant_kernel`` (live HIP events);
@@ -38,7 +42,9 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -239,6 +245,10 @@ class CoreWorkload:
         self.forward()
         self.backward()
 
+    def outputs(self):
+        """What a caller of the step receives: y, A (NCHW / (B,H,W,H+W)), dq, dk, dv NCHW, dgamma."""
+        return {"y": self.y, "A": self.A, "dq": self.dq, "dk": self.dk, "dv": self.dv, "dgamma": self.dgamma}
+
     # ---- single-kernel launches for the roofline object (branch mask restricts to ONE kernel) ----
     def stage_table(self):
         B, C, H, W = self.shape
@@ -325,6 +335,13 @@ class PixelMajorBF16Workload:
         self.forward()
         self.backward()
 
+    def outputs(self):
+        """y (B,H,W,C) bf16, A fp32, dq | dk | dv as the bf16 channel slices of dqkv (B,H,W,ct), dgamma."""
+        cq = self.shape[1] // 8
+        d = self.dqkv
+        return {"y": self.y, "A": self.A, "dq": d[..., :cq], "dk": d[..., cq:2 * cq], "dv": d[..., 2 * cq:],
+                "dgamma": self.dgamma}
+
 
 class PlanesWorkload:
     """The fp32 core on the SPLIT-PLANE path (include/ccnet_cca.h): the step's inputs are what the reference's op gets --
@@ -360,6 +377,13 @@ class PlanesWorkload:
     def step(self):
         self.forward()
         self.backward()
+
+    def outputs(self):
+        """y NCHW, A, dq | dk | dv as the fp32 channel slices of dqkv (B,H,W,ct), dgamma."""
+        cq = self.shape[1] // 8
+        d = self.dqkv
+        return {"y": self.y, "A": self.A, "dq": d[..., :cq], "dk": d[..., cq:2 * cq], "dv": d[..., 2 * cq:],
+                "dgamma": self.dgamma}
 
     def forward(self):
         B, C, H, W = self.shape
@@ -454,6 +478,35 @@ def per_step_stats(fn, iters, flush=None):
         pairs.append((e0, e1))
     torch.cuda.synchronize()
     return quantiles([a.elapsed_time(b) for a, b in pairs])
+
+
+DUMP_SAMPLE = 1 << 20                    # elements kept of a larger output (fixed, seeded sample of its flat indices)
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir, sample=DUMP_SAMPLE):
+    """``--dump-outputs``: every output of the step as ``out_dir/<name>.npy`` in float32 (bf16 widens exactly).  Of an output of
+    more than ``sample`` elements only those at ``sample`` flat indices (sorted, duplicates dropped) drawn by a generator seeded
+    with its name are written, so two builds run with the same arguments write the same positions.  Returns the description
+    that goes on the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    desc, total = {}, 0
+    for name, t in outputs.items():
+        t = t.detach()
+        n = t.numel()
+        if n > sample:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(n, (sample,), generator=g).unique()
+            arr = t.reshape(-1)[idx.to(t.device)].float().cpu().numpy()
+        else:
+            arr = t.float().cpu().numpy()
+        total += arr.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget")
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        desc[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""),
+                      "sampled": n > sample, "written": int(arr.size)}
+    return {"dir": out_dir, "sample_seed": "crc32(name)", "arrays": desc}
 
 
 def capture_step_graph(step_fn):
@@ -1076,7 +1129,12 @@ def main(argv=None, workload_factory=None):
                     help="gloo = host-logic tests on CPU with an injected workload (the product has no CPU path)")
     ap.add_argument("--workload-factory", default=None,
                     help="tests only: 'module:callable' returning an object with .step() (used with --backend gloo)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy, float32; "
+                         "outputs above 2^20 elements as a fixed, seeded sample of their elements")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         rc, parsed = spawn_ranks(args.gpus, argv, args.backend)
@@ -1123,6 +1181,8 @@ def main(argv=None, workload_factory=None):
         cls = PixelMajorBF16Workload if bf16 else PlanesWorkload if use_planes else CoreWorkload
         wl = cls(lib, B, C, H, W, device, shard_seed(1234, rank))
 
+    if args.dump_outputs and not hasattr(wl, "outputs"):
+        sys.exit("bench.py: --dump-outputs needs a workload with .outputs()")
     grads = torch.zeros(CCA_PARAM_FLOATS(C), device=device) if args.allreduce_grads else None
 
     def eager_step():
@@ -1165,6 +1225,8 @@ def main(argv=None, workload_factory=None):
     secs = max_over_ranks(local_s, device, world)
     per_rank = gather_over_ranks({"rank": rank, "ms_per_step": round(local_s / args.steps * 1e3, 4),
                                   **rank_description(device, on_gpu)}, world)
+    # the buffers still hold the last timed step's results: dump them before anything below runs the step again
+    dumped = dump_outputs(wl.outputs(), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     nbytes = core_bytes(B, C, H, W, elt=2 if bf16 else 4)
     value = aggregate_value(nbytes, args.steps, world, secs)
@@ -1199,6 +1261,8 @@ def main(argv=None, workload_factory=None):
         "frac_of_hbm_copy_ceiling": round(value / world / HBM_COPY_GBS, 4),
         "tflops": round(core_flops(B, C, H, W) * world / (ms * 1e-3) / 1e12, 2),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
 
     extras = on_gpu and lib is not None and not args.no_extras
     if extras and bf16 and rank == 0:

@@ -11,7 +11,7 @@ It mirrors ``/root/reference/networks/ccnet.py``:
     CriterionDSN                                            loss/criterion.py:11-35
 
 with the SAME module attribute names, so a ``state_dict`` written by the reference (with the real ``inplace_abn``)
-loads strictly (``tests/test_segmodel.py`` compares the key/shape tables where the reference tree is mounted).
+loads strictly (``tests/test_segmodel.py`` compares the key/shape tables with the reference's, tests/golden/reference_networks.json).
 Only the criss-cross attention inside is hand-written HIP; convolutions, normalisation and the loss are torch ops
 (MIOpen / hipBLASLt), ``InPlaceABNSync`` is this repository's ``inplace_abn`` restatement.
 """

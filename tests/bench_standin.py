@@ -17,8 +17,12 @@ class OracleWorkload:
 
     def step(self):
         y, A = O.cca_core_forward(self.q, self.k, self.v, self.x, self.gamma)
-        O.cca_core_backward(self.dy, self.q, self.k, self.v, A, self.gamma)
+        g = O.cca_core_backward(self.dy, self.q, self.k, self.v, A, self.gamma)
+        self.last = {"y": y, "A": A, **{k: g[k] for k in ("dq", "dk", "dv", "dgamma")}}
         self.steps += 1
+
+    def outputs(self):
+        return self.last
 
 
 def factory(B, C, H, W, device, seed):

@@ -128,3 +128,48 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
 def test_bench_refuses_more_gpus_than_devices():
     p = _run_bench(["--gpus", "8"], _bench_env())                 # nccl backend, no HIP device in this container
     assert p.returncode != 0 and "refusing" in p.stderr
+
+
+def test_bench_dump_outputs_is_the_last_timed_steps_result(tmp_path):
+    """``--dump-outputs DIR``: what the timed path computed, one float32 ``<name>.npy`` per output, the same from run to run
+    (seeded inputs); ``--steps`` is the number of timed steps (no pre-run here: warm-up + timed = every step taken)."""
+    import numpy as np
+    import bench
+    import bench_standin
+    from oracle import cca_oracle as O
+    made = []
+
+    def factory(*a):
+        made.append(bench_standin.factory(*a))
+        return made[-1]
+
+    common = ["--gpus", "1", "--warmup", "2", "--batch", "2", "--channels", "16", "--height", "6", "--width", "5",
+              "--prewarm-s", "0", "--backend", "gloo"]
+    dumps = []
+    for run, steps in enumerate((3, 5)):
+        d = tmp_path / f"run{run}"
+        out = bench.main(common + ["--steps", str(steps), "--dump-outputs", str(d)], workload_factory=factory)
+        assert out["steps"] == steps and made[-1].steps == 2 + steps
+        assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in ("y", "A", "dq", "dk", "dv", "dgamma"))
+        assert set(out["dumped_outputs"]["arrays"]) == {"y", "A", "dq", "dk", "dv", "dgamma"}
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("y", "A", "dq", "dk", "dv", "dgamma")})
+    wl = made[-1]
+    y, A = O.cca_core_forward(wl.q, wl.k, wl.v, wl.x, wl.gamma)
+    g = O.cca_core_backward(wl.dy, wl.q, wl.k, wl.v, A, wl.gamma)
+    want = {"y": y, "A": A, **{n: g[n] for n in ("dq", "dk", "dv", "dgamma")}}
+    for n, t in want.items():
+        assert dumps[0][n].dtype == np.float32 and dumps[0][n].shape == tuple(t.shape), n
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+        assert np.array_equal(dumps[1][n], t.numpy()), n
+    # an output above the sample size: a fixed, seeded sample of its elements, the same positions every time
+    big = {"v": torch.arange(3000, dtype=torch.float32).reshape(30, 100)}
+    d1, d2 = bench.dump_outputs(big, str(tmp_path / "s1"), sample=256), bench.dump_outputs(big, str(tmp_path / "s2"), sample=256)
+    s1, s2 = np.load(tmp_path / "s1" / "v.npy"), np.load(tmp_path / "s2" / "v.npy")
+    assert d1 == {**d2, "dir": d1["dir"]} and d1["arrays"]["v"]["sampled"] and 200 < s1.size <= 256
+    assert s1.dtype == np.float32 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    assert np.isin(s1, big["v"].float().numpy()).all()
+
+
+def test_bench_refuses_zero_steps():
+    p = _run_bench(["--steps", "0", "--backend", "gloo", "--workload-factory", "bench_standin:factory"], _bench_env())
+    assert p.returncode != 0 and "--steps" in p.stderr

@@ -1269,6 +1269,29 @@ def test_bench_bf16_line_has_the_contract_keys(lib, dev):
     assert "pixel-major" in out["config"]["impl"]
 
 
+def test_bench_dump_outputs_are_what_the_timed_step_computed(lib, dev, tmp_path):
+    """bench.py --dump-outputs on the default (split-plane) path at a small shape: the dumped y, A, dq, dk, dv, dgamma are the
+    oracle's on the bench's own seeded inputs (rebuilt here from the same seed)."""
+    import bench
+    B, C, H, W = 1, 128, 100, 61                  # every output below 2^20 elements: dumped whole
+    out = bench.main(["--batch", str(B), "--channels", str(C), "--height", str(H), "--width", str(W), "--steps", "3",
+                      "--warmup", "1", "--prewarm-s", "0", "--no-extras", "--dump-outputs", str(tmp_path)])
+    assert "split-bf16" in out["config"]["impl"] and not any(a["sampled"] for a in out["dumped_outputs"]["arrays"].values())
+    got = {n: torch.from_numpy(np.load(tmp_path / (n + ".npy"))) for n in ("y", "A", "dq", "dk", "dv", "dgamma")}
+    wl = bench.PlanesWorkload(lib, B, C, H, W, dev, bench.shard_seed(1234, 0))
+    cq = C // 8
+    qkv = wl.qkv.cpu().permute(0, 3, 1, 2)
+    q, k, v = (t.contiguous() for t in (qkv[:, :cq], qkv[:, cq:2 * cq], qkv[:, 2 * cq:]))
+    y, A = O.cca_core_forward(q, k, v, wl.x.cpu(), wl.gamma.cpu())
+    g = O.cca_core_backward(wl.dy.cpu(), q, k, v, A, wl.gamma.cpu())
+    pm = lambda t: t.permute(0, 2, 3, 1)                                         # noqa: E731  (NCHW -> pixel-major)
+    want = {"y": y, "A": A, "dq": pm(g["dq"]), "dk": pm(g["dk"]), "dv": pm(g["dv"]), "dgamma": g["dgamma"]}
+    for n, t in want.items():
+        assert got[n].shape == t.shape, n
+    assert all(err(got[n], want[n]) < TOL for n in ("y", "A", "dq", "dk", "dv")), {n: err(got[n], t) for n, t in want.items()}
+    assert float(got["dgamma"]) == pytest.approx(float(want["dgamma"]), rel=1e-3)
+
+
 def test_pixel_major_cores_are_bit_identical_run_to_run(lib, dev):
     """Counted-vmcnt barriers, register-prefetched epilogues, out-of-range DMA lanes: a race would show as run-to-run differences
     under concurrent HBM load (tools/stress_pm.py is the long version, profiles/r02g_stress_pm.log)."""

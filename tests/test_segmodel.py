@@ -1,25 +1,23 @@
 """The callers around the hot path: ``inplace_abn`` restatement, RCCAModule / ResNet-101
 mirror (``ccnet_amd/segmodel.py``) and the synthetic DDP train driver (``ccnet_amd/train_synthetic.py``).
 
-CPU tests compare against the UNMODIFIED reference network code where /root/reference is mounted (the build
-container); the device attention has no CPU path, so on the CPU a test-only module built on the oracle stands in
-for it on OUR side while the reference side runs its own pure-python CrissCrossAttention.  GPU tests (``-m gpu``)
+CPU tests compare against what the UNMODIFIED reference network code computed, recorded under tests/golden/
+(tests/golden/make_network_golden.py: its state_dict table, and its forward + loss with its own pure-python
+CrissCrossAttention); the device attention has no CPU path, so on the CPU a test-only module built on the oracle
+stands in for it on OUR side.  GPU tests (``-m gpu``)
 run the real HIP module inside RCCAModule against the stock-PyTorch formulation on the same device."""
-import importlib
 import json
 import os
 import socket
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 from oracle import cca_oracle as O
-
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 
 
 class OracleCCA(nn.Module):
@@ -49,24 +47,6 @@ def swap_cca(model, cls=OracleCCA):
     return model
 
 
-@pytest.fixture()
-def ref_networks():
-    saved = list(sys.path)
-    mine = ("networks", "utils", "inplace_abn", "cc_attention", "loss")
-    saved_mods = {k: v for k, v in sys.modules.items() if k.split(".")[0] in mine}
-    for k in saved_mods:
-        del sys.modules[k]
-    sys.path[:0] = [REF]                    # the reference's cc_attention AND networks; inplace_abn from this repo
-    sys.path.insert(1, ROOT)
-    try:
-        yield importlib.import_module("networks.ccnet")
-    finally:
-        sys.path[:] = saved
-        for k in [k for k in sys.modules if k.split(".")[0] in mine]:
-            del sys.modules[k]
-        sys.modules.update(saved_mods)
-
-
 def test_abn_is_batchnorm_plus_leaky_relu_and_has_the_real_packages_state_dict_keys():
     from inplace_abn import InPlaceABN, InPlaceABNSync
     torch.manual_seed(0)
@@ -88,53 +68,53 @@ def test_abn_is_batchnorm_plus_leaky_relu_and_has_the_real_packages_state_dict_k
         InPlaceABN(6, activation="swish")
 
 
-@needs_ref
-def test_state_dict_table_equals_the_reference_networks(ref_networks):
+def test_state_dict_table_equals_the_reference_networks():
     """Same keys, same shapes as ``Seg_Model`` of the unmodified networks/ccnet.py (built on this repository's
-    inplace_abn) -> reference checkpoints load strictly."""
+    inplace_abn; tests/golden/reference_networks.json) -> reference checkpoints load strictly."""
     from ccnet_amd.segmodel import Seg_Model
-    theirs = ref_networks.Seg_Model(19, recurrence=2)
+    with open(os.path.join(GOLDEN, "reference_networks.json")) as f:
+        golden = json.load(f)
+    ref = golden["Seg_Model(19,recurrence=2)"]
     ours = Seg_Model(19, recurrence=2)
-    t_ref = {k: tuple(v.shape) for k, v in theirs.state_dict().items()}
+    t_ref = {k: tuple(v["shape"]) for k, v in ref.items()}
     t_our = {k: tuple(v.shape) for k, v in ours.state_dict().items()}
     assert t_our == t_ref
-    res = ours.load_state_dict(theirs.state_dict(), strict=True)
+    g = torch.Generator().manual_seed(0)
+    theirs = {k: torch.randn(*v["shape"], generator=g).to(getattr(torch, v["dtype"])) for k, v in sorted(ref.items())}
+    res = ours.load_state_dict(theirs, strict=True)
     assert not res.missing_keys and not res.unexpected_keys
-    assert sum(p.numel() for p in ours.parameters()) == sum(p.numel() for p in theirs.parameters())
+    assert all(torch.equal(ours.state_dict()[k], v) for k, v in theirs.items())
+    assert sum(p.numel() for p in ours.parameters()) == golden["Seg_Model(19,recurrence=2).parameters"]
 
 
-@needs_ref
-def test_forward_and_loss_match_the_reference_network_on_cpu(ref_networks):
-    """Whole network, eval mode (running statistics, no dropout), 65x65 input -> 9x9 attention maps, R = 2:
-    the reference runs its own pure-python CrissCrossAttention (INF override: functions.py:12 hard-codes .cuda()),
-    ours runs the oracle stand-in.  Then the DSN loss on the same logits."""
+def test_forward_and_loss_match_the_reference_network_on_cpu():
+    """Whole network, eval mode (running statistics, no dropout), 65x65 input -> 9x9 attention maps, R = 2: the logits and
+    DSN loss the reference network computed with its own pure-python CrissCrossAttention on these weights
+    (tests/golden/seg_model_65x65.npz) against ours with the oracle stand-in."""
     from ccnet_amd.segmodel import CriterionDSN, Seg_Model
-    torch.manual_seed(0)
-    theirs = ref_networks.Seg_Model(19, recurrence=2).eval()
-    for m in theirs.modules():
-        if type(m).__name__ == "CrissCrossAttention":
-            m.INF = lambda B, H, W: -torch.diag(torch.tensor(float("inf")).repeat(H), 0).unsqueeze(0).repeat(B * W, 1, 1)
-            with torch.no_grad():
+    z = np.load(os.path.join(GOLDEN, "seg_model_65x65.npz"))
+    torch.manual_seed(0)                     # the weights make_network_golden.py gave the reference network
+    ours = Seg_Model(19, recurrence=2)
+    with torch.no_grad():
+        for m in ours.modules():
+            if type(m).__name__ == "CrissCrossAttention":
                 m.gamma.fill_(0.6)
-    with torch.no_grad():                    # non-trivial running statistics
-        for m in theirs.modules():
+        for m in ours.modules():            # non-trivial running statistics
             if hasattr(m, "running_var"):
                 m.running_mean.normal_(0, 0.1), m.running_var.uniform_(0.8, 1.2)
-    ours = Seg_Model(19, recurrence=2)
-    ours.load_state_dict(theirs.state_dict(), strict=True)
+    state = ours.state_dict()
+    fp = [sum(float(v.double().sum()) for v in state.values()), sum(float(v.double().abs().sum()) for v in state.values())]
+    assert np.allclose(fp, z["fingerprint"], rtol=1e-9), ("seeded weights drifted from the fixture's", fp, z["fingerprint"])
     ours = swap_cca(ours).eval()
-    x = torch.randn(1, 3, 65, 65)
+    x, labels = torch.from_numpy(z["x"]), torch.from_numpy(z["labels"])
+    a = [torch.from_numpy(z["out"]), torch.from_numpy(z["aux"])]
     with torch.no_grad():
-        a, b = theirs(x), ours(x)
+        b = ours(x)
     assert a[0].shape == b[0].shape == (1, 19, 9, 9) and a[1].shape == b[1].shape
     scale = float(a[0].abs().max())
     assert float((a[0] - b[0]).abs().max()) < 1e-4 * max(scale, 1.0)
     assert float((a[1] - b[1]).abs().max()) < 1e-4 * max(float(a[1].abs().max()), 1.0)
-    labels = torch.randint(0, 19, (1, 65, 65))
-    labels[0, :5] = 255
-    crit_ref = importlib.import_module("loss.criterion").CriterionDSN() if os.path.isdir(os.path.join(REF, "loss")) else None
-    if crit_ref is not None:
-        assert float(CriterionDSN()(b, labels)) == pytest.approx(float(crit_ref(a, labels)), rel=1e-4)
+    assert float(CriterionDSN()(b, labels)) == pytest.approx(float(z["loss"][0]), rel=1e-4)
 
 
 def _tiny_factory():

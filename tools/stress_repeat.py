@@ -1,7 +1,7 @@
 """Repeat the fused core fwd+bwd at the headline shape and count runs whose outputs differ from the first run
 (bit-wise) -- a race detector for the counted-vmcnt pipelines.  usage: stress_repeat.py [iters] [B]"""
-import sys, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from ccnet_amd import _lib
 lib = _lib.get_lib(); dev = torch.device('cuda')

@@ -1,6 +1,6 @@
 """GPU check of the strip kernels' entry points against fp64 einsum references (run-to-run identity included)."""
-import sys, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ccnet_amd import _lib
 lib = _lib.CcaLibrary(sys.argv[1]) if len(sys.argv) > 1 else _lib.get_lib()
 dev = torch.device('cuda'); s = torch.cuda.current_stream().cuda_stream
