@@ -7,7 +7,8 @@ device library; the first kernel call does, and fails loudly if it has not been 
 """
 from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFunction, INF, ca_map, ca_softmax,
                         ca_weight, criss_cross_attention, graph_module)
+from .ohem import CriterionOhemDSN, OhemCrossEntropy2d
 
 __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "ca_weight", "ca_map",
-           "ca_softmax", "criss_cross_attention", "graph_module", "INF"]
+           "ca_softmax", "criss_cross_attention", "graph_module", "INF", "OhemCrossEntropy2d", "CriterionOhemDSN"]
 __version__ = "0.1.0"

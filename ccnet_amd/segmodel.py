@@ -180,3 +180,6 @@ class CriterionDSN(nn.Module):
         losses = [F.cross_entropy(F.interpolate(p, size=size, mode="bilinear", align_corners=True), target,
                                   ignore_index=self.ignore_index) for p in preds[:2]]
         return losses[0] if len(losses) == 1 else losses[0] + self.aux_weight * losses[1]
+
+
+from .ohem import CriterionOhemDSN  # noqa: E402,F401  (the --ohem criterion, loss/criterion.py:37-56)

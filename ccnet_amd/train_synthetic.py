@@ -5,6 +5,7 @@ It replaces the reference's ``train.py`` + ``engine.py`` (which need apex-era AP
 the same training step on random data, one process per GPU:
 
     model      ccnet_amd.segmodel.Seg_Model(19, CriterionDSN(), recurrence=2)       train.py:160-164
+               --ohem: CriterionOhemDSN(thresh=--ohem-thres, min_kept=--ohem-keep)   train.py:117-122,168-171
     data       images randn(b,3,769,769), labels randint(0,19) with ~5 % set to 255 train.py:28-33 (crop 769)
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
@@ -61,8 +62,12 @@ def run(args, model_factory=None, quiet=False):
     torch.manual_seed(args.seed + rank)                       # per-rank seed (train.py:154-155)
 
     if model_factory is None:
-        from .segmodel import CriterionDSN, Seg_Model
-        model = Seg_Model(args.num_classes, criterion=CriterionDSN(), recurrence=args.recurrence)
+        from .segmodel import CriterionDSN, CriterionOhemDSN, Seg_Model
+        if getattr(args, "ohem", False):
+            criterion = CriterionOhemDSN(thresh=args.ohem_thres, min_kept=args.ohem_keep)
+        else:
+            criterion = CriterionDSN()
+        model = Seg_Model(args.num_classes, criterion=criterion, recurrence=args.recurrence)
     else:
         model = model_factory()
     model = model.to(device).train()
@@ -118,6 +123,8 @@ def run(args, model_factory=None, quiet=False):
                        "optimizer": "sgd+poly"},
             "final_loss": round(float(loss.detach().float().item()), 4) if loss is not None else None,
         }
+        if getattr(args, "ohem", False):
+            result["criterion"] = "ohem"
         if not quiet:
             print(json.dumps(result), flush=True)
     if ddp and args.destroy_group:
@@ -141,6 +148,10 @@ def build_parser():
                     help="set torch.backends.cudnn.benchmark as train.py:152 does (MIOpen then searches its solvers per convolution "
                          "configuration at first use: minutes with an empty cache); default: leave the process-wide flag untouched")
     ap.add_argument("--no-cudnn-benchmark", dest="cudnn_benchmark", action="store_false")
+    ap.add_argument("--ohem", action="store_true", help="train with CriterionOhemDSN (OHEM cross-entropy on the device), as "
+                                                        "train.py --ohem True")
+    ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
+    ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
     ap.add_argument("--no-destroy-group", dest="destroy_group", action="store_false")
     ap.add_argument("--force-ddp", action="store_true", help="wrap the model in DistributedDataParallel (RCCL process group) even at "
