@@ -1,0 +1,89 @@
+"""ctypes binding of the C ABI declared in include/ccnet_eval.h (the sliding-window evaluation library).
+
+The product loads ``ccnet_amd/csrc_eval/libccnet_eval.so`` (built for gfx950 by ``__graft_entry__.build()``), a library
+of its own beside libccnet_cca.so and libccnet_ohem.so.  As with :mod:`ccnet_amd._lib` there is no fallback: a missing
+library raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import re
+from ctypes import c_char_p, c_int, c_longlong, c_void_p
+from typing import List, Optional
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(_HERE, "csrc_eval")
+LIB_PATH = os.path.join(CSRC, "libccnet_eval.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ccnet_eval.h")
+
+CCNET_EVAL_VERSION = 100       # include/ccnet_eval.h
+MAX_TILES = 64                 # CCNET_EVAL_MAX_TILES
+MAX_CLASSES = 256              # CCNET_EVAL_MAX_CLASSES
+
+_P = c_void_p  # every tensor argument is a raw device pointer (tile_y1x1: a host int array)
+
+# name -> (restype, argtypes); mirrors include/ccnet_eval.h one to one
+_PROTOTYPES = {
+    "ccnet_eval_version": (c_int, []),
+    "ccnet_eval_arch": (c_char_p, []),
+    "ccnet_eval_last_error_string": (c_char_p, []),
+    "ccnet_eval_sliding_f32": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P,
+                                       c_longlong, _P, _P, _P, _P]),
+}
+
+
+def declared_symbols(header: str = HEADER_PATH) -> List[str]:
+    """Every function name include/ccnet_eval.h declares."""
+    with open(header) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(ccnet_\w+)\s*\(", text)))
+
+
+def origins_array(origins):
+    """[(y1, x1), ...] -> the host int array tile_y1x1 of the C ABI (kept alive by the caller for the call)."""
+    flat = [int(v) for yx in origins for v in yx]
+    return (c_int * max(len(flat), 1))(*flat)
+
+
+class EvalError(RuntimeError):
+    pass
+
+
+class EvalLibrary:
+    """A loaded libccnet_eval.so (or, in the CPU tests, the emulator build of the same sources)."""
+
+    def __init__(self, path: str = LIB_PATH):
+        if not os.path.exists(path):
+            raise EvalError(
+                f"{path} not found: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()').  "
+                "ccnet_amd has no CPU or PyTorch fallback for the evaluation kernel.")
+        self.path = path
+        self.dll = ctypes.CDLL(path)
+        for name, (res, args) in _PROTOTYPES.items():
+            fn = getattr(self.dll, name)
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)
+        if self.ccnet_eval_version() != CCNET_EVAL_VERSION:
+            raise EvalError(f"{path} exports C ABI version {self.ccnet_eval_version()}, this binding is written against "
+                            f"{CCNET_EVAL_VERSION} (include/ccnet_eval.h): rebuild the extension")
+
+    def last_error(self) -> str:
+        return self.ccnet_eval_last_error_string().decode()
+
+    def check(self, code: int, what: str = "") -> None:
+        if code != 0:
+            raise EvalError(f"{what or 'ccnet_eval'} failed with code {code}: {self.last_error()}")
+
+
+_lib: Optional[EvalLibrary] = None
+
+
+def get_lib() -> EvalLibrary:
+    """The process-wide device library; raises EvalError when it has not been built."""
+    global _lib
+    if _lib is None:
+        import torch  # noqa: F401  (map PyTorch's HIP runtime first, as _lib.get_lib does)
+        _lib = EvalLibrary(LIB_PATH)
+    return _lib

@@ -1,0 +1,196 @@
+"""Segmentation evaluation on the device: the reference's ``evaluate.py`` (predict_sliding / predict_whole, argmax,
+get_confusion_matrix, mIoU; evaluate.py:102-195, 262-274).
+
+The reference up-samples every tile's logits to the tile size, copies them to the host and accumulates a float64 NHWC score
+map there before ``np.argmax`` and ``np.bincount``.  Here one HIP kernel (include/ccnet_eval.h, libccnet_eval.so) samples
+the tiles' 1/8-resolution logits directly, averages, takes the argmax and counts the confusion matrix on the device, so
+nothing is copied to the host per image.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+from math import ceil
+from typing import List, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _eval_lib
+
+__all__ = ["tile_grid", "predict_sliding", "predict_whole", "SegEvaluator", "shard_indices", "mean_iou",
+           "all_reduce_confusion"]
+
+
+def tile_grid(H: int, W: int, tile_size: Sequence[int]) -> List[Tuple[int, int]]:
+    """The reference's tile origins (y1, x1), rows then columns (evaluate.py:104-124): stride ceil(tile_h * (1 - 1/3)) on
+    both axes, the last tile of a row / column pulled back inside the image.  Unlike the reference, at least one row and
+    one column even where its formula yields none (an image smaller than the tile by a stride or more)."""
+    th, tw = int(tile_size[0]), int(tile_size[1])
+    overlap = 1 / 3
+    stride = ceil(th * (1 - overlap))
+    rows = max(int(ceil((H - th) / stride) + 1), 1)
+    cols = max(int(ceil((W - tw) / stride) + 1), 1)
+    out = []
+    for row in range(rows):
+        for col in range(cols):
+            x1, y1 = int(col * stride), int(row * stride)
+            x2, y2 = min(x1 + tw, W), min(y1 + th, H)
+            out.append((max(int(y2 - th), 0), max(int(x2 - tw), 0)))
+    return out
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _require_device(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("ccnet_amd.evaluate: inputs must be HIP device tensors (there is no CPU fallback for the "
+                               "evaluation kernel)")
+
+
+def cut_tiles(image: torch.Tensor, origins, tile_size, flip: bool) -> torch.Tensor:
+    """(N, 3, H, W) -> (N * (T + T_flip), 3, th, tw): for each image its T zero-padded tiles (pad_image, evaluate.py:95-100),
+    then, with ``flip``, the same tiles of its horizontally flipped copy."""
+    th, tw = int(tile_size[0]), int(tile_size[1])
+    H, W = image.shape[2:]
+    views = [image, image.flip(-1)] if flip else [image]
+    per = []
+    for v in views:
+        for y1, x1 in origins:
+            t = v[:, :, y1:min(y1 + th, H), x1:min(x1 + tw, W)]
+            per.append(F.pad(t, (0, tw - t.shape[3], 0, th - t.shape[2])))
+    return torch.stack(per, 1).reshape(-1, image.shape[1], th, tw)
+
+
+def run_net(net, tiles: torch.Tensor) -> torch.Tensor:
+    """The net over a batch of tiles; ``[0]`` of a list output (evaluate.py:131-132), as contiguous fp32."""
+    out = net(tiles)
+    if isinstance(out, (list, tuple)):
+        out = out[0]
+    return out.to(torch.float32).contiguous()
+
+
+def sliding_call(logits, origins, flip, N, tile_size, H, W, labels=None, ignore_label=255, probs=None, pred=None,
+                 confusion=None):
+    """One ccnet_eval_sliding_f32 launch on the current stream.  ``logits`` (N * (T + T_flip), C, h, w) fp32."""
+    _require_device(logits, labels, probs, pred, confusion)
+    lib = _eval_lib.get_lib()
+    T = len(origins)
+    if T > _eval_lib.MAX_TILES:
+        raise RuntimeError(f"ccnet_amd.evaluate: {T} tiles, the kernel takes at most {_eval_lib.MAX_TILES}")
+    C, h, w = logits.shape[1:]
+    y1x1 = _eval_lib.origins_array(origins)
+    ptr = lambda t: None if t is None else t.data_ptr()                  # noqa: E731
+    lib.check(lib.ccnet_eval_sliding_f32(logits.data_ptr(), T, T if flip else 0, y1x1, N, C, h, w, int(tile_size[0]),
+                                         int(tile_size[1]), H, W, ptr(labels), int(ignore_label), ptr(probs), ptr(pred),
+                                         ptr(confusion), _stream(logits.device)), "ccnet_eval_sliding_f32")
+
+
+def _predict(net, image, tile_size, origins, flip):
+    _require_device(image)
+    N, _, H, W = image.shape
+    logits = run_net(net, cut_tiles(image, origins, tile_size, flip))
+    probs = torch.empty((N, logits.shape[1], H, W), dtype=torch.float32, device=image.device)
+    sliding_call(logits, origins, flip, N, tile_size, H, W, probs=probs)
+    return probs
+
+
+@torch.no_grad()
+def predict_sliding(net, image, tile_size, classes, flip=False):
+    """(N, C, H, W) fp32 device score map: the values of the reference's predict_sliding (which returns (N, H, W, C) float64
+    numpy), each image from its own tiles.  ``flip`` averages with the mirrored image's map (mirrored back along W)."""
+    origins = tile_grid(image.shape[2], image.shape[3], tile_size)
+    probs = _predict(net, image, tile_size, origins, flip)
+    if probs.shape[1] != classes:
+        raise RuntimeError(f"predict_sliding: the net gives {probs.shape[1]} classes, {classes} expected")
+    return probs
+
+
+@torch.no_grad()
+def predict_whole(net, image, flip=False):
+    """predict_whole (evaluate.py:145-153): the net on the whole image, up-sampled to it; one tile of the call above."""
+    H, W = image.shape[2:]
+    return _predict(net, image, (H, W), [(0, 0)], flip)
+
+
+def mean_iou(confusion) -> dict:
+    """evaluate.py:268-274: IU = tp / max(1, pos + res - tp), averaged over all C classes."""
+    cm = confusion.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(confusion) else np.asarray(confusion, np.float64)
+    pos, res, tp = cm.sum(1), cm.sum(0), np.diag(cm)
+    iu = tp / np.maximum(1.0, pos + res - tp)
+    return {"meanIU": float(iu.mean()), "IU_array": iu}
+
+
+def all_reduce_confusion(confusion: torch.Tensor) -> torch.Tensor:
+    """The sum of every rank's matrix when a default process group with world > 1 is up (engine.all_reduce_tensor,
+    norm=False), else the matrix itself.  Over gloo the sum travels through a CPU copy."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() <= 1:
+        return confusion
+    t = confusion.detach().clone()
+    if dist.get_backend() == "gloo":
+        t = t.cpu()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.to(confusion.device)
+
+
+def shard_indices(num_images: int, rank: int, world: int) -> range:
+    """Images rank, rank + world, ...: every image exactly once over the ranks (no DistributedSampler padding)."""
+    return range(rank, num_images, world)
+
+
+class SegEvaluator:
+    """Accumulates the confusion matrix of a segmentation net over batches of (image, label), on the device.
+
+    ``update(net, image, label)`` cuts the batch's tiles (and its flipped copy's), runs the net once over all of them,
+    and counts prediction against label in one kernel; it returns the uint8 (N, H, W) prediction.  ``result()`` returns
+    ``{"meanIU", "IU_array"}`` over every rank of the default process group."""
+
+    def __init__(self, num_classes, ignore_label=255, tile_size=(769, 769), whole=False, flip=False, device=None):
+        if not 1 <= num_classes <= _eval_lib.MAX_CLASSES:
+            raise ValueError(f"SegEvaluator: num_classes {num_classes} outside [1, {_eval_lib.MAX_CLASSES}]")
+        self.num_classes, self.ignore_label = int(num_classes), int(ignore_label)
+        self.tile_size, self.whole, self.flip = (int(tile_size[0]), int(tile_size[1])), bool(whole), bool(flip)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.confusion = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=device)
+
+    def geometry(self, H, W):
+        """(tile origins, tile size) for an H x W image."""
+        if self.whole:
+            return [(0, 0)], (H, W)
+        return tile_grid(H, W, self.tile_size), self.tile_size
+
+    @torch.no_grad()
+    def net_logits(self, net, image):
+        """The net's fp32 (N * (T + T_flip), C, h, w) outputs over every tile of the batch."""
+        _require_device(image)
+        origins, tile = self.geometry(image.shape[2], image.shape[3])
+        if len(origins) > _eval_lib.MAX_TILES:
+            raise RuntimeError(f"SegEvaluator: {len(origins)} tiles, the kernel takes at most {_eval_lib.MAX_TILES}")
+        return run_net(net, cut_tiles(image, origins, tile, self.flip))
+
+    @torch.no_grad()
+    def accumulate(self, logits, label, H, W):
+        """pred and confusion counts from net_logits' output; returns the uint8 (N, H, W) prediction."""
+        _require_device(logits, label, self.confusion)
+        if logits.shape[1] != self.num_classes:
+            raise RuntimeError(f"SegEvaluator: the net gives {logits.shape[1]} classes, {self.num_classes} expected")
+        N = label.shape[0]
+        origins, tile = self.geometry(H, W)
+        pred = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device)
+        sliding_call(logits, origins, self.flip, N, tile, H, W, labels=label.to(torch.int64).contiguous(),
+                     ignore_label=self.ignore_label, pred=pred, confusion=self.confusion)
+        return pred
+
+    def update(self, net, image, label):
+        if label.shape != (image.shape[0],) + tuple(image.shape[2:]):
+            raise RuntimeError(f"SegEvaluator: image {tuple(image.shape)} and label {tuple(label.shape)} do not match")
+        return self.accumulate(self.net_logits(net, image), label, image.shape[2], image.shape[3])
+
+    def reset(self):
+        self.confusion.zero_()
+
+    def result(self):
+        return mean_iou(all_reduce_confusion(self.confusion))

@@ -1,0 +1,329 @@
+"""CPU checks of the sliding-window evaluation (include/ccnet_eval.h, ccnet_amd/csrc_eval/, ccnet_amd/evaluate.py): the
+numpy oracle against the reference fixtures, the tile grid against the reference's loop, the shipped gfx950 library's
+surface, the kernel sources run in the SIMT emulator (tests/emu/ + the primitives of tests/emu_eval/) against the oracle,
+the rank sharding and the confusion reduction over gloo."""
+import ctypes
+import glob
+import os
+import re
+import socket
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import eval_oracle as O
+from conftest import GOLDEN, ROOT
+
+FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "eval_*.npz")))
+SMALL = [f for f in FIXTURES if "recipe" not in f]
+EVAL_CSRC = os.path.join(ROOT, "ccnet_amd", "csrc_eval")
+EMU_DIR = os.path.join(ROOT, "tests", "emu")
+EMU_EVAL_DIR = os.path.join(ROOT, "tests", "emu_eval")
+EMU_LIB = os.path.join(EMU_EVAL_DIR, "libeval_emu.so")
+HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
+LLVM_BIN = "/opt/rocm/lib/llvm/bin"
+
+
+def _id(path):
+    return os.path.basename(path)[:-4]
+
+
+def test_fixtures_cover_the_issue_cases():
+    names = {_id(f) for f in FIXTURES}
+    assert {"eval_1024x2048_t769_c19_recipe", "eval_128x256_t97_c19_multi", "eval_60x80_t97_c19_padded",
+            "eval_300x160_t97_c19_portrait", "eval_128x256_c19_whole", "eval_200x300_t97_c150"} <= names
+    for f in FIXTURES:
+        fx = O.load_fixture(f)
+        assert (fx["label"] == 255).any() and fx["pred"].shape == (1, fx["H"], fx["W"])
+
+
+def _origins(fx):
+    return [(0, 0)] if fx["whole"] else O.reference_tile_grid(int(fx["H"]), int(fx["W"]), fx["tile"])
+
+
+@pytest.mark.parametrize("path", FIXTURES, ids=_id)
+def test_oracle_reproduces_reference_fixture(path):
+    fx = O.load_fixture(path)
+    origins = _origins(fx)
+    probs = O.sliding_scores(O.fixture_tiles(fx, origins), origins, fx["tile"], int(fx["H"]), int(fx["W"]))
+    pred = O.argmax(probs)
+    n_diff = O.check_against_fixture(fx, probs, pred, O.confusion(fx["label"], pred, int(fx["C"])), rel=1e-6)
+    assert n_diff == 0
+
+
+def test_tile_grid_equals_the_reference_loop():
+    from ccnet_amd.evaluate import tile_grid
+    for f in FIXTURES:
+        fx = O.load_fixture(f)
+        if not fx["whole"]:
+            assert tile_grid(fx["H"], fx["W"], fx["tile"]) == O.reference_tile_grid(fx["H"], fx["W"], fx["tile"])
+    assert len(tile_grid(1024, 2048, (769, 769))) == 8
+    n = 0
+    for tile in (33, 97, 129, 385, 513, 769):
+        stride = -(-tile * 2 // 3)
+        for H in (1, 7, tile - stride + 1, tile - 1, tile, tile + 1, 2 * tile + 5, 1024):
+            for W in (1, 13, tile - stride + 1, tile, 3 * tile - 2, 2048):
+                ref = O.reference_tile_grid(H, W, (tile, tile))
+                got = tile_grid(H, W, (tile, tile))
+                if H - tile > -stride and W - tile > -stride:
+                    assert got == ref, (H, W, tile)
+                    n += 1
+                assert len(got) >= 1 and all(0 <= y < H and 0 <= x < W for y, x in got)
+    assert n > 100
+
+
+def test_tile_grid_keeps_one_tile_for_tiny_images():
+    from ccnet_amd.evaluate import tile_grid
+    assert O.reference_tile_grid(10, 10, (769, 769)) == []           # the reference: no tile, a 0/0 score map
+    assert tile_grid(10, 10, (769, 769)) == [(0, 0)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the shipped library
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def eval_lib_path():
+    import __graft_entry__ as g
+    g.build()
+    from ccnet_amd import _eval_lib
+    return _eval_lib.LIB_PATH
+
+
+def test_library_exports_exactly_the_header(eval_lib_path):
+    from ccnet_amd import _eval_lib
+    names = _eval_lib.declared_symbols()
+    assert set(names) == set(_eval_lib._PROTOTYPES) and len(names) == 4
+    out = subprocess.run(["nm", "-D", "--defined-only", eval_lib_path], capture_output=True, text=True, check=True).stdout
+    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == names
+
+
+def test_library_contains_gfx950_code(eval_lib_path):
+    blob = open(eval_lib_path, "rb").read()
+    assert b"gfx950" in blob and b"sliding_kernel" in blob
+
+
+def _code_object_kernels(lib_path, tmp_path):
+    fat, co = str(tmp_path / "eval.fatbin"), str(tmp_path / "eval.co")
+    subprocess.run([f"{LLVM_BIN}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
+    subprocess.run([f"{LLVM_BIN}/clang-offload-bundler", "--unbundle", "--type=o",
+                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
+    notes = subprocess.run([f"{LLVM_BIN}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+    kernels, cur = {}, None
+    for line in notes.splitlines():
+        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
+        if not m:
+            continue
+        key, val = m.group(1), m.group(2)
+        if key == "name":
+            cur = kernels.setdefault(val, {}) if val.startswith("_ZN7segeval") else None
+        elif cur is not None and key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
+            cur[key] = int(val)
+    return kernels
+
+
+@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/clang-offload-bundler"), reason="no LLVM binutils")
+def test_no_kernel_uses_scratch(eval_lib_path, tmp_path):
+    kernels = _code_object_kernels(eval_lib_path, tmp_path)
+    assert len(kernels) == 1, sorted(kernels)
+    bad = {n: k for n, k in kernels.items() if any(k.get(f, 0) for f in ("private_segment_fixed_size", "vgpr_spill_count",
+                                                                           "sgpr_spill_count"))}
+    assert not bad, bad
+
+
+def test_version_and_argument_validation_without_a_gpu(eval_lib_path):
+    from ccnet_amd import _eval_lib
+    lib = _eval_lib.EvalLibrary(eval_lib_path)
+    assert lib.ccnet_eval_version() == 100 and lib.ccnet_eval_arch() == b"gfx950"
+    one = ctypes.c_float(0)
+    p = ctypes.addressof(one)                       # never dereferenced: every call below fails its checks first
+    org = _eval_lib.origins_array([(0, 0)] * 65)
+    call = lib.ccnet_eval_sliding_f32
+    args = dict(T=1, Tf=0, N=1, C=19, h=97, w=97, th=769, tw=769, H=1024, W=2048)
+
+    def run(logits=p, y1x1=org, labels=p, conf=p, **kw):
+        a = dict(args, **kw)
+        return call(logits, a["T"], a["Tf"], y1x1, a["N"], a["C"], a["h"], a["w"], a["th"], a["tw"], a["H"], a["W"], labels,
+                    255, None, None, conf, None)
+
+    assert run(C=257) == -1 and "C=257" in lib.last_error()
+    assert run(C=0) == -1
+    assert run(T=65) == -1 and "T=65" in lib.last_error()
+    assert run(T=0) == -1
+    assert run(T=2, Tf=1) == -1
+    assert run(H=0) == -1 and run(h=0) == -1 and run(N=0) == -1
+    assert run(y1x1=_eval_lib.origins_array([(1024, 0)])) == -1 and "outside" in lib.last_error()
+    assert run(logits=None) == -2
+    assert run(y1x1=None) == -2
+    assert run(labels=None) == -2 and "labels" in lib.last_error()
+    assert lib.last_error().startswith("ccnet_eval:")
+
+
+def test_sources_carry_no_env_knobs_and_no_emulator_code():
+    files = [f for f in os.listdir(EVAL_CSRC) if f.endswith((".hip", ".hpp"))]
+    assert "eval_api.hip" in files and "eval_kernels.hpp" in files
+    for f in files:
+        text = open(os.path.join(EVAL_CSRC, f)).read()
+        assert "getenv" not in text and "CCNET_EMU" not in text and "hip_emu" not in text and "emu::" not in text, f
+
+
+def test_cpu_input_raises_instead_of_falling_back():
+    from ccnet_amd import SegEvaluator, predict_sliding, predict_whole
+    net = O.make_toy_net(19, 0)
+    img = torch.zeros(1, 3, 40, 40)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        predict_sliding(net, img, (33, 33), 19)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        predict_whole(net, img)
+    ev = SegEvaluator(19, device="cpu")
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ev.update(net, img, torch.zeros(1, 40, 40, dtype=torch.long))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the kernel sources in the SIMT emulator
+# ---------------------------------------------------------------------------------------------------------------------
+def _emu_sources():
+    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp")]
+    srcs += [os.path.join(EMU_EVAL_DIR, "eval_platform.hpp"), os.path.join(ROOT, "include", "ccnet_eval.h")]
+    srcs += [os.path.join(EVAL_CSRC, f) for f in os.listdir(EVAL_CSRC) if f.endswith((".hip", ".hpp"))]
+    return srcs
+
+
+@pytest.fixture(scope="module")
+def emu():
+    from ccnet_amd._eval_lib import EvalLibrary
+    stale = not os.path.exists(EMU_LIB) or os.path.getmtime(EMU_LIB) < max(os.path.getmtime(s) for s in _emu_sources())
+    if stale:
+        cxx = HOST_CXX if os.path.exists(HOST_CXX) else "g++"
+        subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
+                        "-I" + EMU_EVAL_DIR, "-I" + EMU_DIR, "-I" + EVAL_CSRC, "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(EVAL_CSRC, "eval_api.hip"), os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB],
+                       check=True, cwd=ROOT)
+    return EvalLibrary(EMU_LIB)
+
+
+def emu_eval(lib, tiles, origins, tile, H, W, flip=False, label=None, C=None, conf=None):
+    """One call of the emulated C ABI with numpy buffers standing in for device memory: (probs, pred, confusion)."""
+    from ccnet_amd._eval_lib import origins_array
+    tiles = np.ascontiguousarray(tiles, np.float32)
+    N, _, C, h, w = tiles.shape
+    probs = np.full((N, C, H, W), np.nan, np.float32)
+    pred = np.full((N, H, W), 0xEE, np.uint8)
+    conf = np.zeros((C, C), np.int64) if conf is None else conf
+    lab = None if label is None else np.ascontiguousarray(label, np.int64)
+    lib.check(lib.ccnet_eval_sliding_f32(tiles.ctypes.data, len(origins), len(origins) if flip else 0, origins_array(origins),
+                                         N, C, h, w, tile[0], tile[1], H, W, None if lab is None else lab.ctypes.data, 255,
+                                         probs.ctypes.data, pred.ctypes.data, None if lab is None else conf.ctypes.data,
+                                         None), "sliding")
+    return probs, pred, conf
+
+
+@pytest.mark.parametrize("path", SMALL, ids=_id)
+def test_emulated_kernel_matches_reference_fixture(emu, path):
+    fx = O.load_fixture(path)
+    origins = _origins(fx)
+    probs, pred, conf = emu_eval(emu, O.fixture_tiles(fx, origins), origins, fx["tile"], int(fx["H"]), int(fx["W"]),
+                                 label=fx["label"])
+    O.check_against_fixture(fx, probs, pred, conf)
+
+
+@pytest.mark.parametrize("case", [
+    dict(N=2, H=70, W=90, tile=33, C=19, flip=False),      # every image its own tiles
+    dict(N=1, H=70, W=90, tile=33, C=19, flip=True),       # flipped pass mirrored back along W
+    dict(N=2, H=20, W=25, tile=33, C=7, flip=True),        # image smaller than the tile, odd C (padded histogram word)
+])
+def test_emulated_kernel_matches_oracle(emu, case):
+    N, H, W, tile, C, flip = (case[k] for k in ("N", "H", "W", "tile", "C", "flip"))
+    from ccnet_amd.evaluate import tile_grid
+    origins = tile_grid(H, W, (tile, tile))
+    rng = np.random.default_rng(H * W + N)
+    h = (tile + 7) // 8
+    tiles = (rng.standard_normal((N, len(origins) * (2 if flip else 1), C, h, h)) * 3).astype(np.float32)
+    _, label = O.make_case_inputs(N, H, W, C, seed=7)
+    ref = O.sliding_scores(tiles, origins, (tile, tile), H, W, flip)
+    probs, pred, conf = emu_eval(emu, tiles, origins, (tile, tile), H, W, flip, label)
+    assert np.abs(probs - ref).max() <= 1e-5 * np.abs(tiles).max()
+    gap = O.top2_gap(ref)
+    diff = pred != O.argmax(ref)
+    assert np.all(gap[diff] < 1e-5 * np.abs(tiles).max())
+    np.testing.assert_array_equal(conf, O.confusion(label, pred, C))       # the counts of its own prediction, exactly
+
+
+def test_emulated_confusion_accumulates_across_calls(emu):
+    fx = O.load_fixture(os.path.join(GOLDEN, "eval_60x80_t97_c19_padded.npz"))
+    origins = _origins(fx)
+    tiles = O.fixture_tiles(fx, origins)
+    _, _, conf = emu_eval(emu, tiles, origins, fx["tile"], 60, 80, label=fx["label"])
+    _, _, conf2 = emu_eval(emu, tiles, origins, fx["tile"], 60, 80, label=fx["label"], conf=conf.copy())
+    np.testing.assert_array_equal(conf2, 2 * conf)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# mIoU, sharding and the distributed reduction
+# ---------------------------------------------------------------------------------------------------------------------
+def test_mean_iou_is_the_reference_formula():
+    from ccnet_amd.evaluate import mean_iou
+    cm = np.array([[5, 1, 0], [2, 3, 0], [0, 0, 0]])
+    r = mean_iou(torch.from_numpy(cm))
+    iu = np.array([5 / (6 + 7 - 5), 3 / (5 + 4 - 3), 0.0])
+    np.testing.assert_allclose(r["IU_array"], iu)
+    assert r["meanIU"] == pytest.approx(iu.mean())                 # averaged over all C classes, the empty one included
+
+
+def test_rank_sharding_takes_every_image_once():
+    from ccnet_amd.evaluate import shard_indices
+    for n in (0, 1, 7, 8, 500):
+        for world in (1, 2, 3, 4, 8):
+            got = sorted(i for r in range(world) for i in shard_indices(n, r, world))
+            assert got == list(range(n))
+    assert list(shard_indices(8, 1, 2)) == [1, 3, 5, 7]
+
+
+def test_eval_driver_flags():
+    from ccnet_amd.eval_synthetic import build_parser
+    a = build_parser().parse_args([])
+    assert (a.images, a.height, a.width, a.tile, a.whole, a.flip, a.recurrence, a.num_classes, a.bf16, a.seed) == \
+        (8, 1024, 2048, 769, False, False, 2, 19, False, 0)
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _reduce_worker(rank, world, port, out):
+    import sys
+    import torch.distributed as dist
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    from ccnet_amd.evaluate import SegEvaluator
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        ev = SegEvaluator(4, device="cpu")
+        ev.confusion += torch.arange(16, dtype=torch.int64).reshape(4, 4) * (rank + 1)
+        r = ev.result()
+        out.put((rank, r["meanIU"], r["IU_array"].tolist(), ev.confusion.tolist()))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_confusion_all_reduce_over_gloo_world_2():
+    import torch.multiprocessing as mp
+    from ccnet_amd.evaluate import mean_iou
+    ctx = mp.get_context("spawn")
+    out = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_reduce_worker, args=(r, 2, port, out)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted(out.get(timeout=120) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    want = mean_iou(torch.arange(16, dtype=torch.int64).reshape(4, 4) * 3)
+    for rank, miou, iu, local in res:
+        assert miou == pytest.approx(want["meanIU"]) and np.allclose(iu, want["IU_array"])
+        assert local == (torch.arange(16).reshape(4, 4) * (rank + 1)).tolist()     # the local counts stay the rank's own

@@ -1,0 +1,201 @@
+"""Sliding-window evaluation on the MI355X (libccnet_eval.so through ccnet_amd.evaluate) against the reference fixtures and
+the numpy oracle: score map, prediction, confusion counts; flip, batches, bf16 net output, small images; a real Seg_Model
+against stock torch; repeatability; no host sync; the eval_synthetic driver on one and two ranks."""
+import glob
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import eval_oracle as O
+from conftest import GOLDEN, ROOT
+
+pytestmark = pytest.mark.gpu
+FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "eval_*.npz")))
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    import __graft_entry__ as g
+    g.build()
+
+
+def device_call(tiles, origins, tile, H, W, flip=False, label=None, probs=True):
+    from ccnet_amd.evaluate import sliding_call
+    t = torch.from_numpy(np.ascontiguousarray(tiles)).to(DEV).flatten(0, 1) if isinstance(tiles, np.ndarray) else tiles
+    N = t.shape[0] // (len(origins) * (2 if flip else 1))
+    C = t.shape[1]
+    p = torch.full((N, C, H, W), float("nan"), device=DEV) if probs else None
+    pred = torch.full((N, H, W), 0xEE, dtype=torch.uint8, device=DEV)
+    conf = torch.zeros((C, C), dtype=torch.int64, device=DEV)
+    lab = None if label is None else torch.from_numpy(label).to(DEV)
+    sliding_call(t, origins, flip, N, tile, H, W, labels=lab, probs=p, pred=pred, confusion=conf if lab is not None else None)
+    torch.cuda.synchronize()
+    return (None if p is None else p.cpu().numpy()), pred.cpu().numpy(), conf.cpu().numpy()
+
+
+def _origins(fx):
+    return [(0, 0)] if fx["whole"] else O.reference_tile_grid(int(fx["H"]), int(fx["W"]), fx["tile"])
+
+
+@pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[:-4])
+def test_fixture_parity(path):
+    fx = O.load_fixture(path)
+    origins = _origins(fx)
+    probs, pred, conf = device_call(O.fixture_tiles(fx, origins), origins, fx["tile"], int(fx["H"]), int(fx["W"]),
+                                    label=fx["label"])
+    n = O.check_against_fixture(fx, probs, pred, conf)
+    print(f"{os.path.basename(path)}: near-tie pixels with a different prediction: {n}")
+
+
+def _check_vs_oracle(tiles, origins, tile, H, W, flip, label, probs, pred, conf):
+    ref = O.sliding_scores(tiles, origins, tile, H, W, flip)
+    tol = 1e-5 * float(np.abs(tiles).max())
+    assert np.abs(probs - ref).max() <= tol
+    diff = pred != O.argmax(ref)
+    assert np.all(O.top2_gap(ref)[diff] < tol)
+    np.testing.assert_array_equal(conf, O.confusion(label, pred, tiles.shape[2]))
+    return int(diff.sum())
+
+
+@pytest.mark.parametrize("N,H,W,tile,C,flip", [
+    (1, 300, 500, 97, 19, True),         # flip
+    (3, 200, 330, 97, 19, False),        # every image its own tiles
+    (2, 40, 50, 97, 19, True),           # image smaller than the tile
+    (1, 257, 513, 129, 150, False),      # ADE20K's class count
+    (1, 120, 160, 97, 256, False),       # the largest C: 128 KiB histogram
+])
+def test_against_oracle(N, H, W, tile, C, flip):
+    from ccnet_amd.evaluate import tile_grid
+    origins = tile_grid(H, W, (tile, tile))
+    rng = np.random.default_rng(N * H + W + C)
+    h = (tile + 7) // 8
+    tiles = (rng.standard_normal((N, len(origins) * (2 if flip else 1), C, h, h)) * 3).astype(np.float32)
+    _, label = O.make_case_inputs(N, H, W, C, seed=H + W)
+    probs, pred, conf = device_call(tiles, origins, (tile, tile), H, W, flip, label)
+    _check_vs_oracle(tiles, origins, (tile, tile), H, W, flip, label, probs, pred, conf)
+
+
+def test_evaluator_bf16_net_output_and_predict_apis():
+    from ccnet_amd import SegEvaluator, predict_sliding, predict_whole
+    from ccnet_amd.evaluate import tile_grid
+    net = O.make_toy_net(19, 3).to(DEV)
+    bf = lambda x: [y.to(torch.bfloat16) for y in net(x)]                     # noqa: E731
+    _, label = O.make_case_inputs(1, 150, 260, 19, seed=3)
+    image = torch.from_numpy(O.make_case_inputs(1, 150, 260, 19, seed=3)[0]).to(DEV)
+    lab = torch.from_numpy(label).to(DEV)
+    for flip in (False, True):
+        ev = SegEvaluator(19, tile_size=(97, 97), flip=flip)
+        logits = ev.net_logits(bf, image)
+        assert logits.dtype == torch.float32
+        pred = ev.update(bf, image, lab)
+        origins = tile_grid(150, 260, (97, 97))
+        tiles = logits.cpu().numpy().reshape(1, -1, 19, 13, 13)
+        ref = O.sliding_scores(tiles, origins, (97, 97), 150, 260, flip)
+        diff = pred.cpu().numpy() != O.argmax(ref)
+        assert np.all(O.top2_gap(ref)[diff] < 1e-5 * np.abs(tiles).max())
+        np.testing.assert_array_equal(ev.confusion.cpu().numpy(), O.confusion(label, pred.cpu().numpy(), 19))
+        r = ev.result()
+        assert 0.0 <= r["meanIU"] <= 1.0 and r["IU_array"].shape == (19,)
+        probs = predict_sliding(net, image, (97, 97), 19, flip=flip)
+        assert probs.shape == (1, 19, 150, 260) and torch.equal(probs.argmax(1).to(torch.uint8).cpu(),
+                                                                torch.from_numpy(O.argmax(probs.cpu().numpy())))
+    whole = predict_whole(net, image)
+    ref = F.interpolate(net(image)[0], size=(150, 260), mode="bilinear", align_corners=True)
+    assert (whole - ref).abs().max().item() <= 1e-5 * ref.abs().max().item()
+
+
+def test_seg_model_evaluator_against_stock_torch():
+    from ccnet_amd import SegEvaluator
+    from ccnet_amd.evaluate import tile_grid
+    from ccnet_amd.segmodel import Seg_Model
+    torch.manual_seed(0)
+    model = Seg_Model(19, recurrence=2).to(DEV).eval()
+    g = torch.Generator(device=DEV).manual_seed(1)
+    image = torch.randn(1, 3, 1024, 2048, device=DEV, generator=g)
+    label = torch.randint(0, 19, (1, 1024, 2048), device=DEV, generator=g)
+    label[torch.rand(1, 1024, 2048, device=DEV, generator=g) < 0.05] = 255
+    ev = SegEvaluator(19)
+    logits = ev.net_logits(model, image)
+    assert logits.shape == (8, 19, 97, 97)
+    pred = ev.accumulate(logits, label, 1024, 2048)
+    # stock torch on the device: F.interpolate per tile, crop, accumulate, divide, argmax, bincount
+    full = torch.zeros(1, 19, 1024, 2048, device=DEV)
+    count = torch.zeros(1, 1, 1024, 2048, device=DEV)
+    for t, (y1, x1) in enumerate(tile_grid(1024, 2048, (769, 769))):
+        up = F.interpolate(logits[t:t + 1], size=(769, 769), mode="bilinear", align_corners=True)
+        y2, x2 = min(y1 + 769, 1024), min(x1 + 769, 2048)
+        full[:, :, y1:y2, x1:x2] += up[:, :, :y2 - y1, :x2 - x1]
+        count[:, :, y1:y2, x1:x2] += 1
+    full /= count
+    stock = full.argmax(1).to(torch.uint8)
+    top2 = full.topk(2, dim=1).values
+    near = (top2[:, 0] - top2[:, 1]) < 1e-5 * logits.abs().max()
+    diff = pred != stock
+    assert not (diff & ~near).any(), int((diff & ~near).sum())
+    keep = (label != 255)
+    ref_cm = torch.bincount((label[keep] * 19 + stock[keep].long()), minlength=361).reshape(19, 19)
+    n = int(diff.sum())
+    d = (ev.confusion - ref_cm).abs()
+    assert int(d.sum()) <= 2 * n and int(d.max()) <= n, (int(d.sum()), n)
+    print(f"Seg_Model 1024x2048: pixels whose prediction differs at a near tie: {n}")
+
+
+def test_bitwise_repeatable():
+    from ccnet_amd.evaluate import tile_grid
+    origins = tile_grid(700, 900, (257, 257))
+    rng = np.random.default_rng(5)
+    tiles = (rng.standard_normal((1, 2 * len(origins), 19, 33, 33)) * 3).astype(np.float32)
+    _, label = O.make_case_inputs(1, 700, 900, 19, seed=5)
+    a = device_call(tiles, origins, (257, 257), 700, 900, True, label)
+    b = device_call(tiles, origins, (257, 257), 700, 900, True, label)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y, equal_nan=True)
+
+
+def test_no_host_sync_in_the_post_processing():
+    from ccnet_amd import SegEvaluator
+    net = O.make_toy_net(19, 4).to(DEV)
+    image = torch.randn(1, 3, 300, 400, device=DEV)
+    label = torch.randint(0, 19, (1, 300, 400), device=DEV)
+    ev = SegEvaluator(19, tile_size=(97, 97), flip=True)
+    logits = ev.net_logits(net, image)
+    ev.accumulate(logits, label, 300, 400)                      # warm: library load, allocator
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        pred = ev.accumulate(logits, label, 300, 400)
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    torch.cuda.synchronize()
+    assert pred.shape == (1, 300, 400) and int(ev.confusion.sum()) == 2 * 300 * 400
+
+
+DRIVER = ["-m", "ccnet_amd.eval_synthetic", "--images", "4", "--height", "256", "--width", "512", "--tile", "193",
+          "--flip"]
+
+
+def _driver(prefix, tmp_path, name):
+    dump = str(tmp_path / f"{name}.pt")
+    r = subprocess.run([sys.executable] + prefix + DRIVER + ["--dump-confusion", dump], cwd=ROOT, capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    return res, torch.load(dump)
+
+
+def test_eval_synthetic_one_and_two_ranks(tmp_path):
+    one, cm1 = _driver([], tmp_path, "one")
+    assert one["n_gpus"] == 1 and one["counted_pixels"] == int(cm1.sum()) > 0 and one["route"], one
+    from ccnet_amd.evaluate import tile_grid
+    assert one["config"]["tiles"] == len(tile_grid(256, 512, (193, 193))) and 0.0 <= one["meanIU"] <= 1.0
+    two, cm2 = _driver(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+                        "--master-port", "29517"], tmp_path, "two")
+    assert two["n_gpus"] == 2, two
+    assert torch.equal(cm1, cm2) and two["meanIU"] == one["meanIU"]
