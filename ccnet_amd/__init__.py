@@ -8,9 +8,11 @@ device library; the first kernel call does, and fails loudly if it has not been 
 from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFunction, INF, ca_map, ca_softmax,
                         ca_weight, criss_cross_attention, graph_module)
 from .evaluate import SegEvaluator, predict_sliding, predict_whole
+from .lovasz import CriterionOhemDSN2, LovaszSoftmax, LovaszSoftmaxFunction, lovasz_softmax
 from .ohem import CriterionOhemDSN, OhemCrossEntropy2d
 
 __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "ca_weight", "ca_map",
            "ca_softmax", "criss_cross_attention", "graph_module", "INF", "OhemCrossEntropy2d", "CriterionOhemDSN",
-           "SegEvaluator", "predict_sliding", "predict_whole"]
+           "SegEvaluator", "predict_sliding", "predict_whole", "lovasz_softmax", "LovaszSoftmax", "LovaszSoftmaxFunction",
+           "CriterionOhemDSN2"]
 __version__ = "0.1.0"

@@ -183,3 +183,4 @@ class CriterionDSN(nn.Module):
 
 
 from .ohem import CriterionOhemDSN  # noqa: E402,F401  (the --ohem criterion, loss/criterion.py:37-56)
+from .lovasz import CriterionOhemDSN2  # noqa: E402,F401  (the --lovasz criterion, loss/criterion.py:59-78)

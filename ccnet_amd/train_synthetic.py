@@ -6,6 +6,7 @@ the same training step on random data, one process per GPU:
 
     model      ccnet_amd.segmodel.Seg_Model(19, CriterionDSN(), recurrence=2)       train.py:160-164
                --ohem: CriterionOhemDSN(thresh=--ohem-thres, min_kept=--ohem-keep)   train.py:117-122,168-171
+               --lovasz: CriterionOhemDSN2 (CE + Lovász-softmax, DSN head unused)   loss/criterion.py:59-78
     data       images randn(b,3,769,769), labels randint(0,19) with ~5 % set to 255 train.py:28-33 (crop 769)
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
@@ -62,8 +63,10 @@ def run(args, model_factory=None, quiet=False):
     torch.manual_seed(args.seed + rank)                       # per-rank seed (train.py:154-155)
 
     if model_factory is None:
-        from .segmodel import CriterionDSN, CriterionOhemDSN, Seg_Model
-        if getattr(args, "ohem", False):
+        from .segmodel import CriterionDSN, CriterionOhemDSN, CriterionOhemDSN2, Seg_Model
+        if getattr(args, "lovasz", False):
+            criterion = CriterionOhemDSN2()
+        elif getattr(args, "ohem", False):
             criterion = CriterionOhemDSN(thresh=args.ohem_thres, min_kept=args.ohem_keep)
         else:
             criterion = CriterionDSN()
@@ -73,8 +76,10 @@ def run(args, model_factory=None, quiet=False):
     model = model.to(device).train()
     net = model
     if ddp:
+        # CriterionOhemDSN2 leaves the DSN head's output unused: DDP must not wait for its gradients
+        extra = {"find_unused_parameters": True} if getattr(args, "lovasz", False) else {}
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if use_cuda else None,
-                                                        broadcast_buffers=False)
+                                                        broadcast_buffers=False, **extra)
     opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.weight_decay)
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed + rank)
@@ -125,6 +130,8 @@ def run(args, model_factory=None, quiet=False):
         }
         if getattr(args, "ohem", False):
             result["criterion"] = "ohem"
+        if getattr(args, "lovasz", False):
+            result["criterion"] = "lovasz"
         if not quiet:
             print(json.dumps(result), flush=True)
     if ddp and args.destroy_group:
@@ -148,8 +155,11 @@ def build_parser():
                     help="set torch.backends.cudnn.benchmark as train.py:152 does (MIOpen then searches its solvers per convolution "
                          "configuration at first use: minutes with an empty cache); default: leave the process-wide flag untouched")
     ap.add_argument("--no-cudnn-benchmark", dest="cudnn_benchmark", action="store_false")
-    ap.add_argument("--ohem", action="store_true", help="train with CriterionOhemDSN (OHEM cross-entropy on the device), as "
-                                                        "train.py --ohem True")
+    crit = ap.add_mutually_exclusive_group()
+    crit.add_argument("--ohem", action="store_true", help="train with CriterionOhemDSN (OHEM cross-entropy on the device), as "
+                                                          "train.py --ohem True")
+    crit.add_argument("--lovasz", action="store_true", help="train with CriterionOhemDSN2: cross-entropy + Lovász-softmax (on the "
+                                                            "device) of the main logits, as loss/criterion.py:59-78")
     ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
     ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
