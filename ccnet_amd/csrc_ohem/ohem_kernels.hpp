@@ -167,7 +167,12 @@ __global__ __launch_bounds__(kPixThreads) void forward_kernel(const float *logit
         float m, s, xt;
         pixel_softmax(logits + (size_t)b * C * HW + r, C, (size_t)HW, t, m, s, xt);
         const float lse = m + logf(s);
-        keep = valid && expf(xt - m) / s <= sc->threshold;
+        // the online sum rescales, so its probability can sit a few ulp off the two-pass value the zoom ranked; near the
+        // threshold the decision takes the two-pass value, so pixels whose key is the k-th (or ties it) are always kept
+        const float thr = sc->threshold;
+        float p = expf(xt - m) / s;
+        if (valid && fabsf(p - thr) <= 1e-4f * thr) p = target_prob(logits, C, 1, HW, b, t, 0, r);
+        keep = valid && p <= thr;
         if (keep) nll = lse - xt;
         pix_lse[i] = lse;
         pix_tgt[i] = keep ? t : -1;

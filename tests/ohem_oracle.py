@@ -114,6 +114,81 @@ def make_case_inputs(B, C, H, W, seed, scale=3.0, ignore_frac=0.05, all_ignored=
     return logits, target
 
 
+# small cases at the edges of the select (tests/test_ohem_host.py runs them in the emulator, tests/test_gpu_ohem.py on the
+# device): C = 19; ``min_kept`` and ``factor`` pick the branch of find_threshold
+EDGE_CASES = [
+    dict(B=1, H=24, W=40, thresh=0.7, min_kept=0, factor=4),                 # min_kept' == 0: thresh alone
+    dict(B=2, H=17, W=33, thresh=0.002, min_kept=16 * 40, factor=4),         # k-th above a low thresh
+    dict(B=1, H=9, W=9, thresh=0.7, min_kept=10 ** 6, factor=8),             # one zoomed pixel: threshold 1.0
+    dict(B=1, H=3, W=30, thresh=0.7, min_kept=100, factor=8),                # zoomed height 0: no keys at all
+    dict(B=1, H=20, W=20, thresh=0.002, min_kept=16 * 20, factor=4, ignore_label=7),   # another ignore label, k-th above
+]
+EDGE_IDS = ["minkept0", "kth_above", "one_zoomed_pixel", "zoomed_height0", "ignore7"]
+
+
+def edge_case_inputs(case):
+    """(logits, target, criterion args) of one EDGE_CASES entry."""
+    case = dict(case)
+    B, H, W = case.pop("B"), case.pop("H"), case.pop("W")
+    logits, target = make_case_inputs(B, 19, H, W, seed=H * W + B)
+    if case.get("ignore_label") == 7:
+        target[target == 255] = 3
+    return logits, target, case
+
+
+def make_tie_inputs(B, C, H, W, seed, n_vectors=12, block=16):
+    """Logits made of ``n_vectors`` distinct per-pixel vectors, each with its own label, constant over ``block`` x ``block``
+    squares: every zoomed sample whose taps lie inside one square repeats its vector's target probability exactly, so the
+    zoomed keys form a few large groups of equal values.  About 3 % of the pixels are ignored."""
+    rng = np.random.default_rng(seed)
+    vec = (rng.standard_normal((n_vectors, C)) * 3).astype(np.float32)
+    lab = rng.integers(0, C, n_vectors)
+    which = rng.integers(0, n_vectors, (B, -(-H // block), -(-W // block)))
+    which = np.repeat(np.repeat(which, block, axis=1), block, axis=2)[:, :H, :W]
+    logits = np.ascontiguousarray(vec[which].transpose(0, 3, 1, 2))
+    target = lab[which].astype(np.int64)
+    target[rng.random((B, H, W)) < 0.03] = 255
+    return logits, target
+
+
+def tie_groups(logits, target, ignore_label=255, factor=8, thresh=0.0):
+    """The groups of equal zoomed keys above ``thresh`` but the largest key, largest group first: a list of (value, keys
+    below it, group size)."""
+    p = zoom_order1(softmax_f32(logits), factor)
+    t = zoom_order0(target, factor).astype(np.int64)
+    valid = t != ignore_label
+    pred = np.take_along_axis(p, np.where(valid, t, 0)[:, None], axis=1)[:, 0][valid]
+    vals, counts = np.unique(pred, return_counts=True)
+    below = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    keep = (vals > thresh) & (below + counts < len(pred))
+    order = np.argsort(-counts[keep], kind="stable")
+    return [(np.float32(v), int(b), int(n)) for v, b, n in zip(vals[keep][order], below[keep][order], counts[keep][order])]
+
+
+def check_result(logits, target, args, threshold, kept_mask, loss, grad, near=1e-6, rtol=1e-5, gtol=1e-5):
+    """The numerics bar of a device result against :func:`ohem` on the same inputs: threshold within 2 fp32 ulp; the kept
+    mask identical except at pixels whose target probability lies within ``near`` of the threshold (the device's expf is
+    not the oracle's exp); loss within ``rtol`` relative and the gradient within ``gtol`` x max|grad| of the oracle on the
+    device's own mask.  Returns (oracle result, number of differing pixels)."""
+    ignore = args.get("ignore_label", 255)
+    o = ohem(logits, target, **args)
+    assert ulp_distance(threshold, o["threshold"]) <= 2, (float(threshold), float(o["threshold"]))
+    diff = kept_mask != (o["new_target"] != ignore)
+    n_diff = int(diff.sum())
+    ref = o
+    if n_diff:
+        assert np.all(np.abs(o["target_prob"][diff] - o["threshold"]) <= near), o["target_prob"][diff]
+        masked = np.where(kept_mask, target, ignore)
+        ref = ohem(logits, masked, ignore_label=ignore, thresh=1.0, min_kept=0, factor=args.get("factor", 8))
+    if np.isnan(ref["loss"]):
+        assert np.isnan(loss) and not kept_mask.any() and np.all(grad == 0)
+    else:
+        assert abs(float(loss) - ref["loss"]) <= rtol * abs(ref["loss"]), (float(loss), ref["loss"])
+        err = float(np.abs(grad - ref["grad"]).max())
+        assert err <= gtol * float(np.abs(ref["grad"]).max()), err
+    return o, n_diff
+
+
 # ---- fixtures (tests/golden/ohem_*.npz, written by tests/golden/make_ohem_golden.py from the reference) ----
 def load_fixture(path):
     """A fixture with its inputs regenerated from the stored seed."""

@@ -204,7 +204,7 @@ def emu():
     return EvalLibrary(EMU_LIB)
 
 
-def emu_eval(lib, tiles, origins, tile, H, W, flip=False, label=None, C=None, conf=None):
+def emu_eval(lib, tiles, origins, tile, H, W, flip=False, label=None, C=None, conf=None, ignore_label=255):
     """One call of the emulated C ABI with numpy buffers standing in for device memory: (probs, pred, confusion)."""
     from ccnet_amd._eval_lib import origins_array
     tiles = np.ascontiguousarray(tiles, np.float32)
@@ -214,7 +214,7 @@ def emu_eval(lib, tiles, origins, tile, H, W, flip=False, label=None, C=None, co
     conf = np.zeros((C, C), np.int64) if conf is None else conf
     lab = None if label is None else np.ascontiguousarray(label, np.int64)
     lib.check(lib.ccnet_eval_sliding_f32(tiles.ctypes.data, len(origins), len(origins) if flip else 0, origins_array(origins),
-                                         N, C, h, w, tile[0], tile[1], H, W, None if lab is None else lab.ctypes.data, 255,
+                                         N, C, h, w, tile[0], tile[1], H, W, None if lab is None else lab.ctypes.data, ignore_label,
                                          probs.ctypes.data, pred.ctypes.data, None if lab is None else conf.ctypes.data,
                                          None), "sliding")
     return probs, pred, conf
@@ -258,6 +258,64 @@ def test_emulated_confusion_accumulates_across_calls(emu):
     _, _, conf = emu_eval(emu, tiles, origins, fx["tile"], 60, 80, label=fx["label"])
     _, _, conf2 = emu_eval(emu, tiles, origins, fx["tile"], 60, 80, label=fx["label"], conf=conf.copy())
     np.testing.assert_array_equal(conf2, 2 * conf)
+
+
+@pytest.mark.parametrize("low_half", [True, False], ids=["low_half", "high_half"])
+def test_emulated_single_cell_counter_saturation(emu, low_half):
+    """111 x 111 pixels, every counted one in the same cell: four workgroups of up to 4096 counts each, in the low or the
+    high 16 bits of the LDS word."""
+    l, a = (2, 4) if low_half else (2, 5)
+    tiles = np.zeros((1, 1, 19, 14, 14), np.float32)
+    tiles[:, :, a] = 10.0
+    label = np.full((1, 111, 111), l, np.int64)
+    label[0, 5, 7:11] = 255
+    label[0, 90, 3] = 19
+    n = int((label == l).sum())
+    assert n >= 3 * 4096 + 17 and ((l * 19 + a) % 2 == 0) == low_half
+    _, pred, conf = emu_eval(emu, tiles, [(0, 0)], (111, 111), 111, 111, label=label)
+    assert np.all(pred == a) and int(conf[l, a]) == n and int(conf.sum()) == n
+
+
+def test_emulated_c256_ignore_outside_and_out_of_range_labels(emu):
+    """C = 256 with ignore -1 counts label 255 and pred 255; with ignore 7 inside [0, C), 7, negative labels and labels
+    >= C are not counted."""
+    from ccnet_amd.evaluate import tile_grid
+    H, W = 40, 50
+    origins = tile_grid(H, W, (33, 33))
+    rng = np.random.default_rng(9)
+    tiles = (rng.standard_normal((1, len(origins), 256, 5, 5)) * 3).astype(np.float32)
+    tiles[:, :, 255] += 4.0
+    label = rng.integers(0, 256, (1, H, W)).astype(np.int64)
+    label[:, :, :10] = 255
+    label[0, 0, :4] = -1
+    _, pred, conf = emu_eval(emu, tiles, origins, (33, 33), H, W, label=label, ignore_label=-1)
+    np.testing.assert_array_equal(conf, O.confusion(label, pred, 256, ignore_label=-1))
+    assert conf[255, 255] > 0 and int(conf.sum()) == H * W - 4
+    label = rng.integers(-300, 300, (1, H, W)).astype(np.int64)
+    label[:, ::3] = 7
+    label[:, 1::3] = rng.integers(0, 19, (1, len(range(1, H, 3)), W))
+    _, pred, conf = emu_eval(emu, tiles[:, :, :19], origins, (33, 33), H, W, label=label, ignore_label=7)
+    np.testing.assert_array_equal(conf, O.confusion(label, pred, 19, ignore_label=7))
+    assert int(conf.sum()) == int(((label != 7) & (label >= 0) & (label < 19)).sum()) and not conf[7].any()
+
+
+@pytest.mark.parametrize("H,W,tile,hw,flip", [
+    (20, 28, (8, 8), (1, 1), True),             # 1 x 1 logits: up-sampling scale 0
+    (40, 60, (33, 41), (5, 6), True),           # non-square tile
+    (60, 20, (33, 33), (5, 5), True),           # narrower than the tile along W only
+], ids=["logits_1x1", "nonsquare_tile", "narrow_w"])
+def test_emulated_degenerate_geometry(emu, H, W, tile, hw, flip):
+    from ccnet_amd.evaluate import tile_grid
+    origins = tile_grid(H, W, tile)
+    rng = np.random.default_rng(H + W)
+    tiles = (rng.standard_normal((1, len(origins) * (2 if flip else 1), 7, hw[0], hw[1])) * 3).astype(np.float32)
+    _, label = O.make_case_inputs(1, H, W, 7, seed=H * W)
+    ref = O.sliding_scores(tiles, origins, tile, H, W, flip)
+    probs, pred, conf = emu_eval(emu, tiles, origins, tile, H, W, flip, label)
+    assert np.abs(probs - ref).max() <= 1e-5 * np.abs(tiles).max()
+    diff = pred != O.argmax(ref)
+    assert np.all(O.top2_gap(ref)[diff] < 1e-5 * np.abs(tiles).max())
+    np.testing.assert_array_equal(conf, O.confusion(label, pred, 7))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

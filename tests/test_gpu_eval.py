@@ -54,13 +54,13 @@ def test_fixture_parity(path):
     print(f"{os.path.basename(path)}: near-tie pixels with a different prediction: {n}")
 
 
-def _check_vs_oracle(tiles, origins, tile, H, W, flip, label, probs, pred, conf):
+def _check_vs_oracle(tiles, origins, tile, H, W, flip, label, probs, pred, conf, ignore_label=255):
     ref = O.sliding_scores(tiles, origins, tile, H, W, flip)
     tol = 1e-5 * float(np.abs(tiles).max())
     assert np.abs(probs - ref).max() <= tol
     diff = pred != O.argmax(ref)
     assert np.all(O.top2_gap(ref)[diff] < tol)
-    np.testing.assert_array_equal(conf, O.confusion(label, pred, tiles.shape[2]))
+    np.testing.assert_array_equal(conf, O.confusion(label, pred, tiles.shape[2], ignore_label))
     return int(diff.sum())
 
 
@@ -80,6 +80,119 @@ def test_against_oracle(N, H, W, tile, C, flip):
     _, label = O.make_case_inputs(N, H, W, C, seed=H + W)
     probs, pred, conf = device_call(tiles, origins, (tile, tile), H, W, flip, label)
     _check_vs_oracle(tiles, origins, (tile, tile), H, W, flip, label, probs, pred, conf)
+
+
+def _random_tiles(N, T, C, h, w, seed):
+    return (np.random.default_rng(seed).standard_normal((N, T, C, h, w)) * 3).astype(np.float32)
+
+
+def test_exactly_64_tiles_with_flip():
+    from ccnet_amd.evaluate import tile_grid
+    origins = tile_grid(552, 552, (97, 97))
+    assert len(origins) == 64                                                   # kMaxTiles
+    tiles = _random_tiles(1, 128, 19, 13, 13, seed=81)
+    _, label = O.make_case_inputs(1, 552, 552, 19, seed=81)
+    out = device_call(tiles, origins, (97, 97), 552, 552, True, label)
+    n = _check_vs_oracle(tiles, origins, (97, 97), 552, 552, True, label, *out)
+    print(f"64 tiles + flip: near-tie prediction differences {n}")
+
+
+def _saturation_case(low_half, C=19):
+    """111 x 111 = 12 321 >= 3 x 4096 + 17 pixels, all predicted `a` and labelled `l` (cell l * C + a even: the low 16 bits
+    of its LDS word; odd: the high 16 bits), plus a few ignored and out-of-range labels that are not counted."""
+    l, a = (2, 4) if low_half else (2, 5)
+    assert ((l * C + a) % 2 == 0) == low_half
+    tiles = np.zeros((1, 1, C, 14, 14), np.float32)
+    tiles[:, :, a] = 10.0
+    label = np.full((1, 111, 111), l, np.int64)
+    label[0, 5, 7:11] = 255
+    label[0, 90, 3] = C
+    return tiles, label, l, a, int((label == l).sum())
+
+
+@pytest.mark.parametrize("low_half", [True, False], ids=["low_half", "high_half"])
+def test_single_cell_counter_saturation(low_half):
+    tiles, label, l, a, n = _saturation_case(low_half)
+    _, pred, conf = device_call(tiles, [(0, 0)], (111, 111), 111, 111, label=label)
+    assert np.all(pred == a) and n >= 3 * 4096 + 17
+    assert int(conf[l, a]) == n and int(conf.sum()) == n
+
+
+def test_c256_with_ignore_label_outside_the_classes():
+    from ccnet_amd.evaluate import sliding_call, tile_grid
+    H, W, C = 120, 150, 256
+    origins = tile_grid(H, W, (97, 97))
+    tiles = _random_tiles(1, len(origins), C, 13, 13, seed=83)
+    tiles[:, :, 255] += 4.0                                                     # pred 255 is common
+    label = np.random.default_rng(84).integers(0, C, (1, H, W)).astype(np.int64)
+    label[:, :, :40] = 255
+    label[0, 0, :10] = -1                                                       # the ignore label
+    t = torch.from_numpy(tiles).to(DEV).flatten(0, 1)
+    pred = torch.empty((1, H, W), dtype=torch.uint8, device=DEV)
+    conf = torch.zeros((C, C), dtype=torch.int64, device=DEV)
+    probs = torch.empty((1, C, H, W), device=DEV)
+    sliding_call(t, origins, False, 1, (97, 97), H, W, labels=torch.from_numpy(label).to(DEV), ignore_label=-1,
+                 probs=probs, pred=pred, confusion=conf)
+    torch.cuda.synchronize()
+    pred, conf = pred.cpu().numpy(), conf.cpu().numpy()
+    _check_vs_oracle(tiles, origins, (97, 97), H, W, False, label, probs.cpu().numpy(), pred, conf, ignore_label=-1)
+    assert conf[255, 255] > 0 and conf[255].sum() >= 40 * H - 10 and int(conf.sum()) == H * W - 10
+
+
+def test_ignore_label_inside_the_classes_and_out_of_range_labels():
+    from ccnet_amd.evaluate import sliding_call, tile_grid
+    H, W, C = 130, 170, 19
+    origins = tile_grid(H, W, (97, 97))
+    tiles = _random_tiles(2, len(origins), C, 13, 13, seed=85)
+    rng = np.random.default_rng(86)
+    label = rng.integers(-300, 300, (2, H, W)).astype(np.int64)                 # rows 2::3: mostly out of range
+    label[:, ::3] = 7                                                           # the ignore label, inside [0, C)
+    label[:, 1::3] = rng.integers(0, C, (2, len(range(1, H, 3)), W))
+    t = torch.from_numpy(tiles).to(DEV).flatten(0, 1)
+    pred = torch.empty((2, H, W), dtype=torch.uint8, device=DEV)
+    conf = torch.zeros((C, C), dtype=torch.int64, device=DEV)
+    sliding_call(t, origins, False, 2, (97, 97), H, W, labels=torch.from_numpy(label).to(DEV), ignore_label=7, pred=pred,
+                 confusion=conf)
+    torch.cuda.synchronize()
+    pred, conf = pred.cpu().numpy(), conf.cpu().numpy()
+    counted = (label != 7) & (label >= 0) & (label < C)
+    assert (label < 0).any() and (label >= C).any() and counted.any()
+    np.testing.assert_array_equal(conf, O.confusion(label, pred, C, ignore_label=7))
+    assert int(conf.sum()) == int(counted.sum()) and not conf[7].any()
+
+
+def test_confusion_accumulates_over_two_device_calls():
+    from ccnet_amd.evaluate import sliding_call, tile_grid
+    H, W, C = 200, 260, 19
+    origins = tile_grid(H, W, (97, 97))
+    tiles = _random_tiles(1, 2 * len(origins), C, 13, 13, seed=87)
+    _, label = O.make_case_inputs(1, H, W, C, seed=87)
+    t = torch.from_numpy(tiles).to(DEV).flatten(0, 1)
+    lab = torch.from_numpy(label).to(DEV)
+    pred = torch.empty((1, H, W), dtype=torch.uint8, device=DEV)
+    conf = torch.zeros((C, C), dtype=torch.int64, device=DEV)
+    sliding_call(t, origins, True, 1, (97, 97), H, W, labels=lab, pred=pred, confusion=conf)
+    one = conf.clone()
+    sliding_call(t, origins, True, 1, (97, 97), H, W, labels=lab, pred=pred, confusion=conf)
+    torch.cuda.synchronize()
+    ref = O.confusion(label, pred.cpu().numpy(), C)
+    np.testing.assert_array_equal(one.cpu().numpy(), ref)
+    np.testing.assert_array_equal(conf.cpu().numpy(), 2 * ref)
+
+
+@pytest.mark.parametrize("H,W,tile,hw,flip", [
+    (40, 56, (8, 8), (1, 1), True),             # 1 x 1 logits: up-sampling scale 0, every tile a constant
+    (300, 420, (97, 129), (13, 17), True),      # non-square tile
+    (300, 60, (97, 97), (13, 13), True),        # narrower than the tile along W only
+    (50, 400, (97, 97), (13, 13), False),       # shorter than the tile along H only
+], ids=["logits_1x1", "nonsquare_tile", "narrow_w", "short_h"])
+def test_degenerate_geometry(H, W, tile, hw, flip):
+    from ccnet_amd.evaluate import tile_grid
+    origins = tile_grid(H, W, tile)
+    tiles = _random_tiles(2, len(origins) * (2 if flip else 1), 19, hw[0], hw[1], seed=H + W)
+    _, label = O.make_case_inputs(2, H, W, 19, seed=H * W)
+    out = device_call(tiles, origins, tile, H, W, flip, label)
+    _check_vs_oracle(tiles, origins, tile, H, W, flip, label, *out)
 
 
 def test_evaluator_bf16_net_output_and_predict_apis():

@@ -67,6 +67,126 @@ def test_no_valid_pixel_gives_zero_loss_and_gradient():
     assert float(loss) == 0.0 and int(m.last_n_kept.item()) == 0 and not grad.any()
 
 
+def _check(n_kept, loss, grad, o):
+    """The bar of test_device_matches_oracle: n_kept exact, loss within 1e-6 relative, gradient within 2 ulp (+0 and -0
+    count as equal).  Returns the largest ulp distance."""
+    assert int(n_kept.item()) == o["n_kept"]
+    assert abs(float(loss) - o["loss"]) <= 1e-6 * abs(o["loss"]) or float(loss) == o["loss"] == 0, (float(loss), o["loss"])
+    g = grad.cpu().numpy() if isinstance(grad, torch.Tensor) else grad
+    ulp = O.ulp_distance(g + np.float32(0), o["grad"] + np.float32(0))             # x + 0 turns -0 into +0
+    worst = int(ulp.max())
+    assert worst <= 2, worst
+    return worst
+
+
+def _run_checked(probas, labels, **args):
+    m, loss, grad = run_device(probas, labels, **args)
+    o = O.lovasz_softmax(probas, labels, **args)
+    worst = _check(m.last_n_kept, loss, grad, o)
+    print(f"{tuple(probas.shape)} {args}: loss {float(loss)!r} (oracle {o['loss']!r}), n_kept {o['n_kept']}, "
+          f"worst gradient distance {worst} ulp")
+    return m, loss, grad.cpu().numpy(), o
+
+
+def test_all_equal_probabilities_give_the_oracle_gradient_bitwise():
+    """One tie group per class: the sorted order is pixel order across 33 tiles and every wave of the scatter."""
+    probas = np.full((2, 19, 129, 257), np.float32(1 / 19), np.float32)
+    labels = np.random.default_rng(51).integers(0, 19, (2, 129, 257)).astype(np.int64)
+    labels[np.random.default_rng(52).random(labels.shape) < 0.05] = 255
+    _, _, g, o = _run_checked(probas, labels, ignore=255)
+    assert np.array_equal(g.view(np.uint32), o["grad"].view(np.uint32))
+
+
+def test_one_valid_pixel():
+    probas, labels = O.make_case_inputs(2, 19, 65, 97, seed=53)
+    labels[:] = 255
+    labels[1, 40, 61] = 7
+    _, _, g, o = _run_checked(probas, labels, ignore=255)
+    assert o["n_kept"] == 1 and np.count_nonzero(g) == 1 and g[1, 7, 40, 61] != 0
+
+
+def test_per_image_with_a_fully_ignored_image():
+    probas, labels = O.make_case_inputs(3, 19, 97, 129, seed=55)
+    labels[1] = 255
+    _, _, g, o = _run_checked(probas, labels, per_image=True, ignore=255)
+    assert not g[1].any() and g[0].any() and g[2].any()
+
+
+@pytest.mark.parametrize("per_image", [False, True], ids=["plain", "per_image"])
+def test_gradient_scales_exactly_with_grad_out(per_image):
+    probas, labels = O.make_case_inputs(2, 19, 97, 129, seed=57)
+    _, l1, g1 = run_device(probas, labels, per_image=per_image, ignore=255)
+    _, l2, g2 = run_device(probas, labels, grad_out=0.5, per_image=per_image, ignore=255)
+    assert torch.equal(l1, l2) and torch.equal(g2, 0.5 * g1)
+
+
+def test_exact_zero_negative_zero_and_one_probabilities():
+    """Where e = |fg - p| = 0 the sign of d e / d p is 0, so the gradient is exactly 0."""
+    probas, labels = O.make_case_inputs(2, 19, 97, 129, seed=59)
+    rng = np.random.default_rng(60)
+    pick = rng.random(probas.shape)
+    probas[pick < 0.1] = 0.0
+    probas[(pick >= 0.1) & (pick < 0.2)] = -0.0
+    fg = labels[:, None] == np.arange(19)[None, :, None, None]
+    probas[fg & (pick >= 0.2) & (pick < 0.6)] = 1.0
+    _, _, g, o = _run_checked(probas, labels, ignore=255)
+    zero_e = (np.abs(fg.astype(np.float32) - probas) == 0) & (labels != 255)[:, None]
+    assert zero_e.sum() > 10000 and not g[zero_e].any()
+
+
+@pytest.mark.parametrize("C,ignore", [(2, 255), (256, None)], ids=["c2", "c256_all_labels"])
+@pytest.mark.parametrize("per_image", [False, True], ids=["plain", "per_image"])
+def test_class_count_limits(C, ignore, per_image):
+    """C = 2 and C = 256 (labels 0..255, none ignored; per_image: finalize takes 512 segments on 256 threads)."""
+    H, W = (129, 257) if C == 2 else (48, 80)
+    probas, labels = O.make_case_inputs(2, C, H, W, seed=61 + C)
+    if C == 256:
+        assert labels.min() == 0 and labels.max() == 255
+    _run_checked(probas, labels, per_image=per_image, ignore=ignore)
+
+
+_SCALE = {}
+
+
+def _scale_inputs():
+    if not _SCALE:
+        _SCALE["x"] = O.make_case_inputs(8, 19, 769, 769, seed=63)
+    return _SCALE["x"]
+
+
+@pytest.mark.parametrize("per_image", [False, True], ids=["plain", "per_image"])
+def test_scale_batch8_769(per_image):
+    """(8, 19, 769, 769): 2 310 sort tiles per plain segment, whose payload index crosses image boundaries."""
+    probas, labels = _scale_inputs()
+    _run_checked(probas, labels, per_image=per_image, ignore=255)
+
+
+@pytest.mark.parametrize("shape", [(1, 2, 4096, 4096), (4, 3, 2048, 2048)], ids=["1x2x4096x4096", "4x3x2048x2048"])
+def test_segment_of_exactly_2_24_pixels(shape):
+    """The limit: 2^24 pixels in one segment (the 24-bit payload index, fp32-exact counts); the second spans four images."""
+    B, C, H, W = shape
+    assert B * H * W == 1 << 24
+    probas, labels = O.make_case_inputs(B, C, H, W, seed=67 + B)
+    _run_checked(probas, labels, ignore=255)
+
+
+def test_two_calls_summed_before_one_backward():
+    """Two losses, each with its own workspace, one backward: every input gets its own oracle gradient."""
+    from ccnet_amd.lovasz import lovasz_softmax
+    p1, t1 = O.make_case_inputs(2, 19, 97, 129, seed=71)
+    p2, t2 = O.make_case_inputs(1, 11, 65, 257, seed=72)
+    x1 = torch.from_numpy(p1).to(DEV).requires_grad_(True)
+    x2 = torch.from_numpy(p2).to(DEV).requires_grad_(True)
+    s1, s2 = {}, {}
+    l1 = lovasz_softmax(x1, torch.from_numpy(t1).to(DEV), ignore=255, stats=s1)
+    l2 = lovasz_softmax(x2, torch.from_numpy(t2).to(DEV), classes="all", per_image=True, ignore=255, stats=s2)
+    (l1 + l2).backward()
+    torch.cuda.synchronize()
+    for x, stats, loss, p, t, args in ((x1, s1, l1, p1, t1, dict(ignore=255)),
+                                       (x2, s2, l2, p2, t2, dict(classes="all", per_image=True, ignore=255))):
+        _check(stats["n_kept"], loss.detach(), x.grad, O.lovasz_softmax(p, t, **args))
+
+
 def test_criterion_against_reference_fixture_and_oracle_composition():
     from ccnet_amd.segmodel import CriterionOhemDSN2
     z = np.load(CRITERION_FIXTURE)

@@ -117,6 +117,63 @@ def test_bf16_logits_give_fp32_loss_and_bf16_gradient():
     assert (grad.float().cpu().numpy() - o["grad"]).__abs__().max() <= 1e-2 * np.abs(o["grad"]).max()
 
 
+def _run_checked(logits, target, grad_out=1.0, **args):
+    """One device forward + backward checked against the oracle (O.check_result); returns (module, loss, grad, oracle)."""
+    m, loss, grad = run_device(logits, target, grad_out=grad_out, **args)
+    g = grad.cpu().numpy()
+    mask = (g != 0).any(axis=1)
+    assert int(m.last_kept.item()) == int(mask.sum())
+    o, n_diff = O.check_result(logits, target, args, m.last_threshold.item(), mask, float(loss.item()), g)
+    assert int(m.last_num_valid.item()) == o["num_valid"]
+    print(f"{tuple(logits.shape)}: threshold {m.last_threshold.item()!r} (oracle {float(o['threshold'])!r}), kept "
+          f"{int(mask.sum())}, mask pixels differing near the threshold {n_diff}")
+    return m, loss, g, o
+
+
+@pytest.mark.parametrize("case", O.EDGE_CASES, ids=O.EDGE_IDS)
+def test_edge_cases_match_oracle(case):
+    logits, target, args = O.edge_case_inputs(case)
+    _run_checked(logits, target, **args)
+
+
+def test_all_ignored_gives_nan_loss_zero_gradient_and_threshold_one():
+    logits, target = O.make_case_inputs(2, 19, 40, 56, seed=3, all_ignored=True)
+    m, loss, grad = run_device(logits, target, thresh=0.7, min_kept=0, factor=4)
+    assert math.isnan(float(loss)) and float(m.last_threshold.item()) == 1.0
+    assert int(m.last_kept.item()) == 0 and int(m.last_num_valid.item()) == 0 and not grad.any()
+
+
+def test_gradient_scales_exactly_with_grad_out():
+    logits, target = O.make_case_inputs(2, 19, 97, 129, seed=11)
+    _, l1, g1 = run_device(logits, target, thresh=0.7, min_kept=20000)
+    _, l2, g2 = run_device(logits, target, grad_out=0.5, thresh=0.7, min_kept=20000)
+    assert torch.equal(l1, l2) and torch.equal(g2, 0.5 * g1)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 4, 6])
+def test_tie_group_at_the_kth_key_is_kept_whole(seed):
+    """Logits from a few per-pixel vectors: large groups of equal zoomed keys.  The k-th key is the last of its group, so
+    one rank more would select the next larger value; the group itself must be kept whole at full resolution."""
+    logits, target = O.make_tie_inputs(2, 19, 128, 192, seed=seed)
+    groups = [g for g in O.tie_groups(logits, target, factor=4, thresh=0.002) if g[2] >= 4][:6]
+    assert groups
+    for value, below, size in groups:
+        args = dict(thresh=0.002, min_kept=(below + size) * 16, factor=4)
+        m, _, g, o = _run_checked(logits, target, **args)
+        assert o["threshold"] == value
+        group = o["valid"] & (o["target_prob"] == value)
+        assert group.sum() >= size and (g != 0).any(axis=1)[group].all(), (float(value), size)
+
+
+@pytest.mark.parametrize("shape,args", [
+    ((8, 19, 769, 769), dict(thresh=0.6, min_kept=200000, factor=8)),       # the training driver's --ohem recipe
+    ((2, 150, 257, 385), dict(thresh=0.7, min_kept=50000, factor=8)),       # ADE20K's class count
+], ids=["recipe_b8", "c150"])
+def test_scale_matches_oracle(shape, args):
+    logits, target = O.make_case_inputs(*shape, seed=sum(shape))
+    _run_checked(logits, target, **args)
+
+
 def test_train_synthetic_ohem_child_process():
     cmd = [sys.executable, "-m", "ccnet_amd.train_synthetic", "--ohem", "--steps", "2", "--warmup", "1", "--size", "257"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)

@@ -324,3 +324,28 @@ def test_emulated_gradient_scales_with_grad_out_and_repeats_bitwise(emu):
     c = emu_lovasz(emu, probas, labels, ignore=255, grad_out=0.5)
     assert a["loss"] == b["loss"] and np.array_equal(a["grad"], b["grad"])
     np.testing.assert_array_equal(c["grad"], 0.5 * a["grad"])
+
+
+def test_emulated_exact_zero_negative_zero_and_one_probabilities(emu):
+    """Where e = |fg - p| = 0 the sign of d e / d p is 0, so the gradient is exactly 0 (+0 and -0 compare equal)."""
+    probas, labels = O.make_case_inputs(1, 4, 50, 90, seed=31)
+    pick = np.random.default_rng(32).random(probas.shape)
+    fg = labels[:, None] == np.arange(4)[None, :, None, None]
+    probas[pick < 0.1] = 0.0
+    probas[(pick >= 0.1) & (pick < 0.2)] = -0.0
+    probas[fg & (pick >= 0.2) & (pick < 0.6)] = 1.0
+    r = emu_lovasz(emu, probas, labels, ignore=255)
+    o = O.lovasz_softmax(probas, labels, ignore=255)
+    assert r["n_kept"] == o["n_kept"] and abs(r["loss"] - o["loss"]) <= 1e-6 * abs(o["loss"])
+    assert int(O.ulp_distance(r["grad"] + np.float32(0), o["grad"] + np.float32(0)).max()) <= 2
+    zero_e = (np.abs(fg.astype(np.float32) - probas) == 0) & (labels != 255)[:, None]
+    assert zero_e.sum() > 1000 and not r["grad"][zero_e].any()
+
+
+@pytest.mark.parametrize("C,ignore", [(2, 255), (256, None)], ids=["c2", "c256_all_labels"])
+@pytest.mark.parametrize("per_image", [False, True], ids=["plain", "per_image"])
+def test_emulated_class_count_limits(emu, C, ignore, per_image):
+    H, W = (48, 90) if C == 2 else (8, 16)
+    probas, labels = O.make_case_inputs(2, C, H, W, seed=33 + C)
+    args = dict(per_image=per_image, ignore=ignore)
+    check_emulated(emu_lovasz(emu, probas, labels, **args), O.lovasz_softmax(probas, labels, **args))

@@ -196,19 +196,9 @@ def test_emulated_kernels_match_reference_fixture(emu, path):
     O.check_against_fixture(fx, r["threshold"], mask, r["loss"], r["grad"])
 
 
-@pytest.mark.parametrize("case", [
-    dict(B=1, H=24, W=40, thresh=0.7, min_kept=0, factor=4),                 # min_kept' == 0: thresh alone
-    dict(B=2, H=17, W=33, thresh=0.002, min_kept=16 * 40, factor=4),         # k-th above a low thresh
-    dict(B=1, H=9, W=9, thresh=0.7, min_kept=10 ** 6, factor=8),             # one zoomed pixel: threshold 1.0
-    dict(B=1, H=3, W=30, thresh=0.7, min_kept=100, factor=8),                # zoomed height 0: no keys at all
-    dict(B=1, H=20, W=20, thresh=0.002, min_kept=16 * 20, factor=4, ignore_label=7),   # another ignore label, k-th above
-])
+@pytest.mark.parametrize("case", O.EDGE_CASES)
 def test_emulated_edge_cases_match_oracle(emu, case):
-    case = dict(case)
-    B, H, W = case.pop("B"), case.pop("H"), case.pop("W")
-    logits, target = O.make_case_inputs(B, 19, H, W, seed=H * W + B)
-    if case.get("ignore_label") == 7:
-        target[target == 255] = 3
+    logits, target, case = O.edge_case_inputs(case)
     r = emu_ohem(emu, logits, target, **case)
     o = O.ohem(logits, target, **case)
     assert r["num_valid"] == o["num_valid"]
@@ -217,6 +207,20 @@ def test_emulated_edge_cases_match_oracle(emu, case):
     np.testing.assert_array_equal(mask, o["new_target"] != case.get("ignore_label", 255))
     assert abs(r["loss"] - o["loss"]) <= 1e-5 * abs(o["loss"])
     assert np.abs(r["grad"] - o["grad"]).max() <= 1e-5 * np.abs(o["grad"]).max()
+
+
+def test_emulated_tie_group_at_the_kth_key_is_kept_whole(emu):
+    """Many equal zoomed keys; the k-th is the last of its group, so one rank more selects the next larger value."""
+    logits, target = O.make_tie_inputs(1, 19, 128, 192, seed=2)
+    groups = [g for g in O.tie_groups(logits, target, factor=4, thresh=0.002) if g[2] >= 4][:6]
+    assert len(groups) >= 3
+    for value, below, size in groups:
+        args = dict(thresh=0.002, min_kept=(below + size) * 16, factor=4)
+        r = emu_ohem(emu, logits, target, **args)
+        mask = kept_mask_from_grad(r["grad"])
+        o, _ = O.check_result(logits, target, args, r["threshold"], mask, r["loss"], r["grad"])
+        group = o["valid"] & (o["target_prob"] == value)
+        assert o["threshold"] == value and group.sum() >= size and mask[group].all(), (value, int(mask[group].sum()))
 
 
 def test_emulated_all_ignored_gives_nan_loss_and_zero_gradient(emu):
