@@ -1,6 +1,7 @@
 """Synthetic-data evaluation driver: the reference's ``evaluate.py`` (Cityscapes val mIoU) on seeded random images.
 
-    model      ccnet_amd.segmodel.Seg_Model(num_classes, recurrence=R), random init (seeded) or --restore-from, eval mode
+    model      ccnet_amd.segmodel.Seg_Model(num_classes, recurrence=R), random init (seeded) or --restore-from, eval mode;
+               --abn device|inplace swaps its inplace_abn layers for the HIP twins (ccnet_amd.abn.convert_abn)
     data       image i: randn(1, 3, H, W), labels randint(0, C) with ~5 % set to 255, from a generator seeded with seed + i
     inference  SegEvaluator: the 8 zero-padded 769^2 tiles of a 1024 x 2048 image (--whole: the image itself), --flip adds
                the mirrored image's tiles; one net call per image, one HIP kernel for the score, argmax and confusion
@@ -50,7 +51,12 @@ def run(args, quiet=False):
     model = Seg_Model(args.num_classes, recurrence=args.recurrence)
     if args.restore_from:
         load_model(model, args.restore_from)
+    if args.abn in ("device", "inplace"):
+        from .abn import convert_abn
+        convert_abn(model, args.abn)
     model = model.to(device).eval()
+    if args.abn is not None:
+        torch.cuda.reset_peak_memory_stats(device)
     routes = set()
     model.head.cca.register_forward_pre_hook(lambda m, inp: routes.add(m.route(inp[0])))
     ev = SegEvaluator(args.num_classes, tile_size=(args.tile, args.tile), whole=args.whole, flip=args.flip, device=device)
@@ -105,6 +111,9 @@ def run(args, quiet=False):
                        "weights": "restored" if args.restore_from else "random"},
             "counted_pixels": int(counts.sum()),
         }
+        if args.abn is not None:
+            result["abn"] = args.abn
+            result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
         if args.dump_confusion:
             torch.save(counts, args.dump_confusion)
         if not quiet:
@@ -126,6 +135,10 @@ def build_parser():
     ap.add_argument("--num-classes", type=int, default=19)
     ap.add_argument("--bf16", action="store_true", help="run the net under bf16 autocast (the kernel reads its output as fp32)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--abn", choices=("torch", "device", "inplace"), default=None,
+                    help="normalisation layers: torch (the default: the stock inplace_abn restatement), device or inplace "
+                         "(the HIP ABN kernels, ccnet_amd.abn.convert_abn); when given, the JSON line also reports abn and "
+                         "max_memory_allocated_mb")
     ap.add_argument("--restore-from", type=str, default=None, help="checkpoint for Seg_Model (segmodel.load_model)")
     ap.add_argument("--warmup", type=int, default=1, help="1: one untimed, uncounted image first")
     ap.add_argument("--dump-confusion", type=str, default=None, help="tests: torch.save the reduced confusion matrix here")

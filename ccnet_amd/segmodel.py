@@ -13,7 +13,9 @@ It mirrors ``/root/reference/networks/ccnet.py``:
 with the SAME module attribute names, so a ``state_dict`` written by the reference (with the real ``inplace_abn``)
 loads strictly (``tests/test_segmodel.py`` compares the key/shape tables with the reference's, tests/golden/reference_networks.json).
 Only the criss-cross attention inside is hand-written HIP; convolutions, normalisation and the loss are torch ops
-(MIOpen / hipBLASLt), ``InPlaceABNSync`` is this repository's ``inplace_abn`` restatement.
+(MIOpen / hipBLASLt), ``InPlaceABNSync`` is this repository's ``inplace_abn`` restatement.  ``ccnet_amd.abn.convert_abn``
+swaps those for device ABNs; with out-of-place device ABNs the residual units and the stem fuse their relu (and ``bn3``'s
+residual add) into the ABN kernels.
 """
 from __future__ import annotations
 
@@ -57,6 +59,11 @@ class Bottleneck(nn.Module):
                            if project else None)
 
     def forward(self, x):
+        if getattr(self.bn3, "fused_epilogues", False):
+            # device ABNs (ccnet_amd.abn.convert_abn(model, "device")): relu, and bn3's residual add, fused into the layers
+            y = self.bn1(self.conv1(x), activation="relu")
+            y = self.bn2(self.conv2(y), activation="relu")
+            return self.bn3(self.conv3(y), residual=x if self.downsample is None else self.downsample(x), activation="relu")
         y = F.relu(self.bn1(self.conv1(x)))
         y = F.relu(self.bn2(self.conv2(y)))
         y = self.bn3(self.conv3(y))
@@ -118,9 +125,14 @@ class ResNetCCNet(nn.Module):
         self.recurrence = recurrence
 
     def forward(self, x, labels=None):
-        x = F.relu(self.bn1(self.conv1(x)))
-        x = F.relu(self.bn2(self.conv2(x)))
-        x = F.relu(self.bn3(self.conv3(x)))
+        if getattr(self.bn1, "fused_epilogues", False):         # device ABNs: the stem's relu fused as in Bottleneck
+            x = self.bn1(self.conv1(x), activation="relu")
+            x = self.bn2(self.conv2(x), activation="relu")
+            x = self.bn3(self.conv3(x), activation="relu")
+        else:
+            x = F.relu(self.bn1(self.conv1(x)))
+            x = F.relu(self.bn2(self.conv2(x)))
+            x = F.relu(self.bn3(self.conv3(x)))
         x = self.layer2(self.layer1(self.maxpool(x)))
         x = self.layer3(x)
         aux = self.dsn(x)

@@ -7,6 +7,7 @@ the same training step on random data, one process per GPU:
     model      ccnet_amd.segmodel.Seg_Model(19, CriterionDSN(), recurrence=2)       train.py:160-164
                --ohem: CriterionOhemDSN(thresh=--ohem-thres, min_kept=--ohem-keep)   train.py:117-122,168-171
                --lovasz: CriterionOhemDSN2 (CE + Lovász-softmax, DSN head unused)   loss/criterion.py:59-78
+               --abn device|inplace: every inplace_abn layer swapped for its HIP twin (ccnet_amd.abn.convert_abn)
     data       images randn(b,3,769,769), labels randint(0,19) with ~5 % set to 255 train.py:28-33 (crop 769)
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
@@ -73,7 +74,13 @@ def run(args, model_factory=None, quiet=False):
         model = Seg_Model(args.num_classes, criterion=criterion, recurrence=args.recurrence)
     else:
         model = model_factory()
+    abn_mode = getattr(args, "abn", None)
+    if abn_mode in ("device", "inplace"):
+        from .abn import convert_abn
+        convert_abn(model, abn_mode)
     model = model.to(device).train()
+    if use_cuda and abn_mode is not None:
+        torch.cuda.reset_peak_memory_stats(device)
     net = model
     if ddp:
         # CriterionOhemDSN2 leaves the DSN head's output unused: DDP must not wait for its gradients
@@ -103,12 +110,17 @@ def run(args, model_factory=None, quiet=False):
             torch.cuda.synchronize()
 
     loss = None
+    losses = []                                               # (--abn given) every step's loss, read after the timed window
     for it in range(args.warmup):
         loss = step(it)
+        if abn_mode is not None:
+            losses.append(loss.detach())
     fence()
     t0 = time.perf_counter()
     for it in range(args.warmup, total):
         loss = step(it)
+        if abn_mode is not None:
+            losses.append(loss.detach())
     fence()
     elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -132,6 +144,11 @@ def run(args, model_factory=None, quiet=False):
             result["criterion"] = "ohem"
         if getattr(args, "lovasz", False):
             result["criterion"] = "lovasz"
+        if abn_mode is not None:
+            result["abn"] = abn_mode
+            result["step_losses"] = [round(float(v.float().item()), 6) for v in losses]
+            if use_cuda:
+                result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
         if not quiet:
             print(json.dumps(result), flush=True)
     if ddp and args.destroy_group:
@@ -160,6 +177,11 @@ def build_parser():
                                                           "train.py --ohem True")
     crit.add_argument("--lovasz", action="store_true", help="train with CriterionOhemDSN2: cross-entropy + Lovász-softmax (on the "
                                                             "device) of the main logits, as loss/criterion.py:59-78")
+    ap.add_argument("--abn", choices=("torch", "device", "inplace"), default=None,
+                    help="normalisation layers: torch (the default: the stock inplace_abn restatement), device (the HIP ABN "
+                         "kernels, out of place, relu and residual adds fused in the residual units) or inplace (HIP ABN "
+                         "kernels writing over their input, gamma = |weight| + eps); when given, the JSON line also reports "
+                         "abn, step_losses and max_memory_allocated_mb")
     ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
     ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
