@@ -2,6 +2,7 @@
 """bench.py -- criss-cross attention fwd+bwd throughput on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full   # + every extra leg (roofline, cpu_baseline, imgs_per_s, ...)
     python bench.py --gpus 8 --steps 50 --warmup 10          # self-spawns 8 ranks (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -24,7 +25,10 @@ every step.
 in float32, a fixed, seeded sample of the elements of any output above 2^20 of them (under 64 MB in all).  The inputs are
 seeded, so two builds run with the same arguments can be compared output for output.
 
-Rank 0 prints ONE JSON line: the driver contract plus
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it sets up, warms up, times the steps,
+writes ``--dump-outputs`` and prints the driver contract, with what follows from the timed steps alone (``per_rank``,
+``collective_library``, shares of the HBM roofline and ``tflops`` at the measured step time).  ``--full`` adds every leg that
+takes runs of its own, among them
   ``roofline``      op-level: SURVEY 8(d) algorithmic bytes of one step / the step time, against 8 TB/s; the
                     slowest single launch is described under ``roofline.dominant_kernel`` (live HIP events);
   ``cpu_baseline``  the CPU oracle timed on a bounded sample on this box's host cores;
@@ -32,7 +36,10 @@ Rank 0 prints ONE JSON line: the driver contract plus
                     step (ccnet_amd.train_synthetic, DDP over RCCL when N > 1), whole-job images/s;
   ``step_ms_stats`` median / p10 / p90 of per-step HIP-event times, warm (back to back) and cold (a 512 MiB
                     buffer rewritten between steps, so nothing of the step's tensors survives in the 256 MiB
-                    Infinity Cache).
+                    Infinity Cache);
+and the launch accounting, ``gpu_probe``, the other kernel family, bf16 configs[4], small batches, the RCCA head, the projection
+GEMMs, the module and the stock-PyTorch formulation.  ``--no-extras``, ``--no-train`` and ``--no-cpu-baseline`` trim a ``--full``
+run.
 """
 import argparse
 import hashlib
@@ -1108,8 +1115,12 @@ def main(argv=None, workload_factory=None):
                     help="bf16 = BASELINE.json configs[4]: pixel-major bf16 core, default shape (16,512,129,129)")
     ap.add_argument("--allreduce-grads", action="store_true",
                     help="all-reduce the module's 7 parameter gradients after every step (engine.py:75)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every extra leg (roofline, launch accounting, gpu_probe, other "
+                         "precisions and sizes, module, stock PyTorch, cpu_baseline, train step); off: the headline line only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline/module/cpu/train legs (timed region only)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip roofline/module/cpu/train legs (timed region only, as without --full)")
     ap.add_argument("--no-train", action="store_true", help="skip the synthetic train-step leg (imgs_per_s)")
     ap.add_argument("--train-steps", type=int, default=4)
     ap.add_argument("--train-batch", type=int, default=1, help="images per GPU in the train leg (engine.py:88: 8/world)")
@@ -1264,7 +1275,8 @@ def main(argv=None, workload_factory=None):
     if dumped is not None:
         out["dumped_outputs"] = dumped
 
-    extras = on_gpu and lib is not None and not args.no_extras
+    # everything below takes runs of its own: a plain run stops at the headline (its line is printed at the end)
+    extras = on_gpu and lib is not None and args.full and not args.no_extras
     if extras and bf16 and rank == 0:
         out["step_ms_stats"] = {"warm": per_step_stats(step, 50)}
         out.update(launch_accounting(lib, wl, graph))

@@ -1258,15 +1258,21 @@ def test_small_batch_k_split_at_the_headline_geometry(lib, dev, B):
 
 
 def test_bench_bf16_line_has_the_contract_keys(lib, dev):
-    """bench.py --dtype bf16 (BASELINE configs[4]) on a small shape: one JSON-able dict with the contract's keys."""
+    """bench.py --dtype bf16 (BASELINE configs[4]) on a small shape: one JSON-able dict with the contract's keys.  A plain run
+    stops there; --full adds the legs that take runs of their own, the roofline among them."""
     import bench
-    out = bench.main(["--dtype", "bf16", "--batch", "2", "--channels", "64", "--height", "33", "--width", "18", "--steps", "3",
-                      "--warmup", "1", "--prewarm-s", "0.05", "--no-train", "--no-cpu-baseline"])
-    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                "vs_baseline", "dtype", "data", "config", "roofline"):
-        assert key in out, key
-    assert out["dtype"] == "bf16" and out["value"] > 0 and out["roofline"]["bound"] == "hbm"
-    assert "pixel-major" in out["config"]["impl"]
+    common = ["--dtype", "bf16", "--batch", "2", "--channels", "64", "--height", "33", "--width", "18", "--steps", "3",
+              "--warmup", "1", "--prewarm-s", "0.05"]
+    plain = bench.main(common)
+    full = bench.main(common + ["--full", "--no-train", "--no-cpu-baseline"])
+    for out in (plain, full):
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                    "vs_baseline", "dtype", "data", "config"):
+            assert key in out, key
+        assert out["dtype"] == "bf16" and out["value"] > 0
+        assert "pixel-major" in out["config"]["impl"]
+    assert full["roofline"]["bound"] == "hbm" and "step_ms_stats" in full and "launch_ms" in full
+    assert not {"roofline", "step_ms_stats", "launch_ms", "fwd_ms", "bwd_ms"} & set(plain), sorted(plain)
 
 
 def test_bench_dump_outputs_are_what_the_timed_step_computed(lib, dev, tmp_path):

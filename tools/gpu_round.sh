@@ -16,7 +16,7 @@ echo "== smoke"; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 
 echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -m gpu -q -rA --no-header -p no:cacheprovider "$@" > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest_gpu.log"
 grep -E "^(PASSED|FAILED|ERROR)|passed|failed|headline max-abs" "$OUT/pytest_gpu.log" | tail -60
 
-echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"
+echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"
 
 echo "== rocprofv3 kernel stats"
 cd /tmp && export TMPDIR=/tmp

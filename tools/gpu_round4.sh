@@ -14,10 +14,10 @@ echo "== ab_options"; timeout 600 python tools/ab_options.py > "$OUT/ab_options.
 echo "== pytest -m gpu"; timeout 1800 python -m pytest tests -m gpu -q -rA --no-header -p no:cacheprovider -x > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest_gpu.log"
 grep -E "^(FAILED|ERROR)|passed|failed|headline max-abs|logit-scale|vs the ORACLE|Error|error" "$OUT/pytest_gpu.log" | tail -40
 if [ "$MODE" = "quick" ]; then
-  echo "== bench (no extras)"; timeout 600 python bench.py --gpus 1 --steps 50 --warmup 10 --no-train --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; head -c 3000 "$OUT/bench.json"; tail -5 "$OUT/bench.err"
+  echo "== bench (no extras)"; timeout 600 python bench.py --gpus 1 --steps 50 --warmup 10 --full --no-train --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; head -c 3000 "$OUT/bench.json"; tail -5 "$OUT/bench.err"
   exit 0
 fi
-echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; head -c 6000 "$OUT/bench.json"; tail -5 "$OUT/bench.err"
+echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; head -c 6000 "$OUT/bench.json"; tail -5 "$OUT/bench.err"
 echo "== rocprofv3 kernel stats"
 cd /tmp && export TMPDIR=/tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -- python "$R/bench.py" --steps 20 --warmup 5 --no-extras > "$OUT/prof_bench.json" 2> "$OUT/prof.err"; echo "rocprof rc=$?"

@@ -13,7 +13,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 echo "== host: $(nproc) cores; $(lscpu | grep 'Model name' | sed 's/.*: *//')" | tee "$OUT/host.txt"
 rocm-smi --showmaxpower --showpower --showclocks --showperflevel > "$OUT/rocm_smi_idle.txt" 2>&1
 echo "== smoke"; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?" | tee -a "$OUT/smoke.log"; tail -4 "$OUT/smoke.log"
-echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 --no-train $([ "$MODE" = "hunt" ] && echo --no-cpu-baseline) > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -5 "$OUT/bench.err"
+echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 --full --no-train $([ "$MODE" = "hunt" ] && echo --no-cpu-baseline) > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -5 "$OUT/bench.err"
 python3 - "$OUT/bench.json" <<'PY'
 import json, sys
 try:
@@ -35,7 +35,7 @@ if [ "$MODE" = "hunt" ]; then
 fi
 [ "$MODE" = "slowset" ] || { echo "== pytest -m gpu"; timeout 1800 python -m pytest tests -m gpu -q -rA --no-header -p no:cacheprovider > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest_gpu.log"
 grep -E "^(FAILED|ERROR)|passed|failed|headline max-abs|logit-scale|vs the ORACLE|Error|error" "$OUT/pytest_gpu.log" | tail -60; }
-echo "== bench, bf16 configs[4]"; timeout 600 python bench.py --dtype bf16 --steps 30 --warmup 5 --no-train --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"; head -c 700 "$OUT/bench_bf16.json"; echo
+echo "== bench, bf16 configs[4]"; timeout 600 python bench.py --dtype bf16 --steps 30 --warmup 5 --full --no-train --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"; head -c 700 "$OUT/bench_bf16.json"; echo
 echo "== bf16 partial A/B"; timeout 600 python tools/bf16_partial_ab.py > "$OUT/bf16_partial_ab.txt" 2>&1; grep "==\|partial vs" "$OUT/bf16_partial_ab.txt"
 [ "$MODE" = "quick" ] && exit 0
 echo "== ab_options"; timeout 900 python tools/ab_options.py > "$OUT/ab_options.txt" 2>&1; echo "ab rc=$?"; grep "==" "$OUT/ab_options.txt"; grep " us " "$OUT/ab_options.txt" | head -30

@@ -20,7 +20,7 @@ tests)
   echo "== pytest -m gpu"; timeout 1800 python -m pytest tests -m gpu -q -rA --durations=25 --no-header -p no:cacheprovider ${PYTEST_ARGS:-} > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest_gpu.log"
   grep -E "^(FAILED|ERROR)|passed|failed|headline max-abs|scale sweep|vs the ORACLE|Error|error" "$OUT/pytest_gpu.log" | tail -70;;
 bench)
-  echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 ${BENCH_ARGS:---no-train} > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -3 "$OUT/bench.err"
+  echo "== bench"; timeout 900 python bench.py --gpus 1 --steps 50 --warmup 10 --full ${BENCH_ARGS:---no-train} > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -3 "$OUT/bench.err"
   python3 - "$OUT/bench.json" <<'PY'
 import json, sys
 try:
@@ -35,7 +35,7 @@ except Exception as e:
 PY
   ;;
 bf16)
-  echo "== bench, bf16 configs[4]"; timeout 600 python bench.py --dtype bf16 --steps 30 --warmup 5 --no-train --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"; head -c 700 "$OUT/bench_bf16.json"; echo;;
+  echo "== bench, bf16 configs[4]"; timeout 600 python bench.py --dtype bf16 --steps 30 --warmup 5 --full --no-train --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"; head -c 700 "$OUT/bench_bf16.json"; echo;;
 prof)
   echo "== rocprofv3 kernel stats"
   cd /tmp && export TMPDIR=/tmp
