@@ -263,7 +263,8 @@ __global__ __launch_bounds__(kThreads) void stats_finalize_kernel(const T *x, co
     const double n = (double)N * (double)HW, dm = s1 / n;
     local[c] = n;
     local[C + c] = (double)Elem<T>::get(x, (size_t)c * HW) + dm;
-    local[2 * C + c] = fmax(s2 - s1 * dm, 0.0);
+    const double m2 = s2 - s1 * dm;
+    local[2 * C + c] = m2 < 0.0 ? 0.0 : m2;          // clamps negative rounding residue; a NaN stays (fmax would return 0)
 }
 
 __global__ __launch_bounds__(kThreads) void stats_combine_kernel(const double *all, int R, int C, float eps, float momentum,

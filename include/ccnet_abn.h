@@ -30,7 +30,17 @@
  * be reused by the next call.  Tolerance bar against a float64 oracle of the same arithmetic: fp32 1e-5 relative to the
  * output's scale for y and the statistics, 1e-4 for dweight, dbias and dx (dx against the scale of
  * gamma invstd dz); bf16 tensors: y within 2^-7 and the gradients within 2^-6 of their scale (bf16 rounding of the
- * stored tensors).
+ * stored tensors).  For CCNET_ABN_FROM_OUTPUT "the same arithmetic" is the rebuild itself: the oracle starts, as the
+ * kernels do, from the y that was stored (rounded to fp32 or bf16) and computes act^-1, xhat, act' and the two sums from it
+ * in float64; against that oracle dx and dresidual meet the bar above and dweight, dbias and the sums meet 1e-4 in both
+ * dtypes.  Against the EXACT gradients (those of the unrounded forward pass) in-place mode also carries the rounding of the
+ * stored y amplified by the inverse activation: not at all for leaky_relu (y / p keeps y's relative rounding), for elu by
+ * about e^-z = 1 / (1 + y / p), which grows until y / p reaches the clamp at z = log(2^-24) = -16.6; every z below it is
+ * rebuilt as -16.6.  With elu in fp32 the exact dx is met to 1e-4 while z stays above about -16 and is off by 1e-2 of its
+ * scale beyond; in bf16 (y + p has 8 bits) by 3e-3 at weight 1 and by a few 1e-2 from weight 4.  dweight and dbias are
+ * sums of dz, which elu' = y + p damps where the inverse amplifies, and stay within the bar (DESIGN.md section 14 has the
+ * figures).  A NaN or an infinity in x makes its own channel's variance, invstd and running variance NaN and its mean and
+ * running mean NaN (or the infinity), as in any batch norm, and leaves every other channel's bits alone.
  *
  * No host synchronisation; every launch on `stream` (NULL = the default stream).
  * Return codes: 0 ok, -1 bad descriptor or argument, -2 NULL pointer, -3 workspace too small, -4 launch failure

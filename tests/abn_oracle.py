@@ -84,6 +84,50 @@ def backward(f, dy, weight, training, eps=1e-5, act=IDENTITY, p=0.01, gamma_mode
             "sum_dz": sdz, "sum_dzx": sdzx}
 
 
+def act_inverse(y, act, p):
+    """z from y as include/ccnet_abn.h specifies it: leaky y / p, elu log1p(max(y / p, -1 + 2^-24)), y itself above 0"""
+    if act == LEAKY_RELU:
+        return np.where(y > 0, y, y / p)
+    if act == ELU:
+        return np.where(y > 0, y, np.log1p(np.maximum(np.minimum(y, 0.0) / p, -1.0 + 2.0 ** -24)))
+    return y
+
+
+def act_grad_from_output(y, act, p):
+    """d act / dz taken from the output y (y > 0: 1; else relu 0, leaky p, elu y + p)"""
+    if act == RELU:
+        return (y > 0).astype(np.float64)
+    if act == LEAKY_RELU:
+        return np.where(y > 0, 1.0, p)
+    if act == ELU:
+        return np.where(y > 0, 1.0, y + p)
+    return np.ones_like(y)
+
+
+def backward_from_output(y, dy, residual, weight, bias, mean, invstd, n, training, act=IDENTITY, p=0.01, eps=1e-5):
+    """CCNET_ABN_FROM_OUTPUT in float64: the gradients rebuilt from a stored (and so rounded) output ``y`` -- the y the code
+    under test produced -- with gamma = |weight| + eps: z = act^-1(y), xhat = (z - beta - residual) / gamma, act' from y.
+    ``mean`` is unused by the arithmetic (xhat comes from y) and is taken for symmetry with backward(); dict(dx, dweight,
+    dbias, dresidual, sum_dz, sum_dzx)."""
+    y = np.asarray(y, np.float64)
+    shape = y.shape
+    N, C = shape[:2]
+    y3 = y.reshape(N, C, -1)
+    g = gamma_of(weight, C, 1, eps)
+    b = np.zeros(C) if bias is None else np.asarray(bias, np.float64)
+    z = act_inverse(y3, act, p)
+    r = 0.0 if residual is None else np.asarray(residual, np.float64).reshape(N, C, -1)
+    xhat = (z - _bc(b) - r) / _bc(g)
+    dz = np.asarray(dy, np.float64).reshape(N, C, -1) * act_grad_from_output(y3, act, p)
+    sdz = dz.sum(axis=(0, 2))
+    sdzx = (dz * xhat).sum(axis=(0, 2))
+    k = _bc(g * np.asarray(invstd, np.float64))
+    dx = k * (dz - _bc(sdz / n) - xhat * _bc(sdzx / n)) if training else k * dz
+    w = np.ones(C) if weight is None else np.asarray(weight, np.float64)
+    return {"dx": dx.reshape(shape), "dweight": sdzx * np.sign(w), "dbias": sdz, "dresidual": dz.reshape(shape),
+            "sum_dz": sdz, "sum_dzx": sdzx, "z": z, "xhat": xhat}
+
+
 def to_bf16_bits(a):
     """float -> bf16 bit pattern (uint16), round to nearest even"""
     u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abn_cases as K
 import abn_oracle as O
 from conftest import ROOT
 
@@ -228,94 +229,12 @@ def emu():
     return AbnLibrary(EMU_LIB)
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data
+def emu_abn(lib, x, weight, bias, rm, rv, dy, **kw):
+    """forward + backward through the emulated C ABI, numpy buffers standing in for device memory (abn_cases.run_abn)"""
+    return K.run_abn(lib, K.HostMemory(), x, weight, bias, rm, rv, dy, **kw)
 
 
-def emu_abn(lib, x, weight, bias, rm, rv, dy, training=True, act=0, p=0.01, gamma_mode=0, eps=1e-5, momentum=0.1,
-            residual=None, source=0, bf16=False, ranks=1):
-    """forward + backward through the emulated C ABI, numpy buffers standing in for device memory.  ``source`` 1 rebuilds
-    xhat from y, which is written over x (in place).  ``ranks`` > 1 splits the batch into that many 'ranks' whose
-    statistics and sums are exchanged as the Python layer does."""
-    from ccnet_amd._abn_lib import make_desc
-    N, C = x.shape[:2]
-    HW = int(np.prod(x.shape[2:]))
-    conv = (lambda a: O.to_bf16_bits(a)) if bf16 else (lambda a: np.array(a, np.float32))      # copies: y may overwrite x
-    back = (lambda a: O.from_bf16_bits(a)) if bf16 else (lambda a: a)
-    xs = np.array_split(conv(x).reshape(N, C, HW), ranks)
-    rs = None if residual is None else np.array_split(conv(residual).reshape(N, C, HW), ranks)
-    dys = np.array_split(conv(dy).reshape(N, C, HW), ranks)
-    w = None if weight is None else np.ascontiguousarray(weight, np.float32)
-    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
-    rm, rv = np.array(rm, np.float32), np.array(rv, np.float32)
-    descs = [make_desc(int(bf16), len(xr), C, HW, 1, act, p, gamma_mode, eps) for xr in xs]
-    wss = [np.full(lib.ccnet_abn_workspace_bytes(ctypes.byref(d)) // 8 + 1, np.nan) for d in descs]
-    saved = None
-    if training:
-        local = np.full((ranks, 3, C), np.nan)
-        for r in range(ranks):
-            lib.check(lib.ccnet_abn_stats(ctypes.byref(descs[r]), _ptr(xs[r]), local[r].ctypes.data, _ptr(wss[r]),
-                                          wss[r].nbytes, None), "stats")
-        saved = np.full((3, C), np.nan)
-        lib.check(lib.ccnet_abn_stats_combine(ctypes.byref(descs[0]), local.ctypes.data, ranks, momentum, _ptr(rm), _ptr(rv),
-                                              saved.ctypes.data, None), "combine")
-    ys = []
-    for r in range(ranks):
-        y = xs[r] if source == 1 else np.zeros_like(xs[r])
-        lib.check(lib.ccnet_abn_forward(ctypes.byref(descs[r]), _ptr(xs[r]), _ptr(None if rs is None else rs[r]), _ptr(y),
-                                        _ptr(saved), _ptr(rm), _ptr(rv), _ptr(w), _ptr(b), None), "forward")
-        ys.append(y)
-    sums = np.full((ranks, 2, C), np.nan)
-    dws, dbs = np.full((ranks, C), np.nan, np.float32), np.full((ranks, C), np.nan, np.float32)
-    for r in range(ranks):
-        src = ys[r] if source == 1 else xs[r]
-        lib.check(lib.ccnet_abn_backward_reduce(ctypes.byref(descs[r]), source, _ptr(src), _ptr(ys[r]), _ptr(dys[r]),
-                                                _ptr(None if rs is None else rs[r]), _ptr(saved), _ptr(rm), _ptr(rv),
-                                                _ptr(w), _ptr(b), sums[r].ctypes.data, dws[r].ctypes.data,
-                                                dbs[r].ctypes.data, _ptr(wss[r]), wss[r].nbytes, None), "reduce")
-    dxs, dress = [], []
-    for r in range(ranks):
-        src = ys[r] if source == 1 else xs[r]
-        dx = np.zeros_like(xs[r])
-        dres = np.zeros_like(xs[r]) if residual is not None else None
-        lib.check(lib.ccnet_abn_backward_apply(ctypes.byref(descs[r]), source, _ptr(src), _ptr(ys[r]), _ptr(dys[r]),
-                                               _ptr(None if rs is None else rs[r]), _ptr(saved), _ptr(rm), _ptr(rv), _ptr(w),
-                                               _ptr(b), sums.ctypes.data, ranks, _ptr(dx), _ptr(dres), None), "apply")
-        dxs.append(dx)
-        dress.append(dres)
-    out = {"y": back(np.concatenate(ys)).reshape(x.shape), "dx": back(np.concatenate(dxs)).reshape(x.shape),
-           "dweight": dws.sum(0), "dbias": dbs.sum(0), "running_mean": rm, "running_var": rv, "saved": saved,
-           "sums": sums.sum(0)}
-    if residual is not None:
-        out["dresidual"] = back(np.concatenate(dress)).reshape(x.shape)
-    return out
-
-
-def _close(a, b, tol, name, scale=None):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    scale = max(np.abs(b).max(), scale or 0.0, 1e-30)
-    err = np.abs(a - b).max() / scale
-    assert err <= tol, (name, err, tol)
-
-
-def _case(shape, seed, mean=0.0, scale=1.0, residual=False):
-    rng = np.random.default_rng(seed)
-    C = shape[1]
-    x = (rng.standard_normal(shape) * scale + mean).astype(np.float32)
-    w = rng.uniform(-1.5, 1.5, C).astype(np.float32)
-    b = rng.uniform(-0.5, 0.5, C).astype(np.float32)
-    rm = rng.uniform(-0.2, 0.2, C).astype(np.float32)
-    rv = rng.uniform(0.5, 2.0, C).astype(np.float32)
-    dy = rng.standard_normal(shape).astype(np.float32)
-    res = rng.standard_normal(shape).astype(np.float32) if residual else None
-    return x, w, b, rm, rv, dy, res
-
-
-def dx_scale(f, g, w, gamma_mode, eps=1e-5):
-    """the scale dx is measured against: that of gamma invstd dz (dx itself nearly cancels at two values per channel)"""
-    k = O.gamma_of(w, len(f["invstd"]), gamma_mode, eps) * f["invstd"]
-    dz = g["dresidual"].reshape(g["dresidual"].shape[0], len(k), -1)
-    return float(np.abs(dz * k[None, :, None]).max())
+_close, _case, dx_scale = K.close, K.make_inputs, K.dx_scale
 
 
 def check_against_oracle(r, x, w, b, rm, rv, dy, res, training, act, p, gamma_mode, eps=1e-5, bf16=False, tol=None,
@@ -431,3 +350,64 @@ def test_emulated_misaligned_pointers_take_the_element_path(emu):
                                     w.ctypes.data, b.ctypes.data, None))
     f = O.forward(x, w, b, rm, rv, True)
     _close(y.reshape(x.shape), f["y"], 1e-5, "y")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the shared case table (tests/abn_cases.py) through the emulator; tests/test_gpu_abn_edges.py runs it on the device
+# ---------------------------------------------------------------------------------------------------------------------
+DTYPES = pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+
+
+@DTYPES
+@pytest.mark.parametrize("shape,sem", K.GRID_CASES, ids=lambda v: v)
+def test_emulated_edge_shapes(emu, shape, sem, bf16):
+    K.run_grid_case(emu, K.HostMemory(), shape, sem, bf16)
+
+
+@DTYPES
+@pytest.mark.parametrize("par,shape,sem", K.PARAMETER_CASES, ids=lambda v: v)
+def test_emulated_parameter_forms(emu, par, shape, sem, bf16):
+    K.run_parameter_case(emu, K.HostMemory(), par, shape, sem, bf16)
+
+
+@pytest.mark.parametrize("name,shape,bf16", K.NUMERIC_CASES, ids=lambda v: {False: "f32", True: "bf16"}.get(v, v))
+def test_emulated_numeric_edges(emu, name, shape, bf16):
+    K.run_numeric_case(emu, K.HostMemory(), name, shape, bf16)
+
+
+@DTYPES
+@pytest.mark.parametrize("sem,shape", K.MISALIGNED_CASES, ids=lambda v: v)
+def test_emulated_misaligned_tensors_give_the_aligned_result_bitwise(emu, sem, shape, bf16):
+    K.run_misaligned_case(emu, K.HostMemory(), sem, shape, bf16)
+
+
+@pytest.mark.parametrize("N,R,sem", K.RANK_CASES, ids=lambda v: str(v))
+def test_emulated_uneven_ranks_match_one(emu, N, R, sem):
+    K.run_rank_case(emu, K.HostMemory(), N, R, sem)
+
+
+@pytest.mark.parametrize("sem", ["oop_relu_res", "ip_leaky01_res"])
+def test_emulated_non_finite_input_stays_in_its_channel_and_in_its_statistics(emu, sem):
+    K.run_nonfinite_case(emu, K.HostMemory(), sem)
+
+
+def test_guard_bands_catch_a_store_outside_the_tensor():
+    """the driver's own check: a write one element before or after a buffer's data is seen"""
+    mem = K.HostMemory()
+    for kind, dtype in (("f32", np.float32), ("bf16", np.uint16), ("f64", np.float64)):
+        for where in (-1, 5):
+            q = K.Buf(mem, "t", kind, 5, offset=1, data=np.zeros(5, dtype))
+            assert q.read(dtype)[1]
+            q.raw.view(np.uint8)[q.start + where * q.size] ^= 1
+            assert not q.read(dtype)[1], (kind, where)
+
+
+def test_in_place_design_error_is_what_the_header_states():
+    """the two oracles alone, no kernel: from-output on the exact y rounded to storage, against the exact gradients"""
+    e = {(act, bf16, w): K.in_place_design_error(act, p, float(w), bf16)
+         for act, p in ((O.ELU, 1.0), (O.LEAKY_RELU, 0.01)) for bf16 in (False, True) for w in (1, 4, 8, 20)}
+    assert all(e[O.LEAKY_RELU, False, w]["dx"] <= 1e-7 for w in (1, 4, 8, 20))         # leaky_relu loses nothing
+    assert e[O.ELU, False, 1]["dx"] <= 1e-6 and e[O.ELU, False, 4]["dx"] <= 1e-4       # elu: fine while z > -16 ...
+    assert e[O.ELU, False, 4]["min_z"] > -16.6 > e[O.ELU, False, 8]["min_z"]
+    assert e[O.ELU, False, 8]["dx"] > 1e-3 and e[O.ELU, False, 20]["dx"] > 1e-3        # ... and off the bar beyond
+    assert all(v[k] <= (2 ** -6 if bf16 else 1e-4) for (_, bf16, _), v in e.items() for k in ("dweight", "dbias"))
