@@ -398,12 +398,13 @@ def split_planes(t: torch.Tensor, c0: int, C: int, layout: int = PLANES_HL, dtyp
     """Channels [c0, c0 + C) of the fp32 pixel-major tensor ``t`` (B, H, W, ps) as SPLIT PLANES (B, H, W, n, C):
     bf16 hi | lo halves of every value (include/ccnet_cca.h, "split-plane path"), produced once for all their consumers
     (``layout`` HLH / HHL: the three-plane rows of a K-concatenated split-bf16 GEMM; ``dtype`` bfloat16 for those)."""
-    B, H, W, ps = t.shape
+    t, bs, ps = _pm_view("split_planes source", t, torch.float32)      # (a view that does not qualify is copied)
+    B, H, W, _ = t.shape
     n = 2 if layout == PLANES_HL else 3
     out = torch.empty((B, H, W, n, C), device=t.device, dtype=dtype)
     lib = _lib.get_lib()
     with torch.cuda.device(t.device):
-        lib.check(lib.ccnet_cca_split_planes_f32(t.data_ptr() + 4 * c0, out.data_ptr(), B, C, H, W, t.stride(0), t.stride(2),
+        lib.check(lib.ccnet_cca_split_planes_f32(t.data_ptr() + 4 * c0, out.data_ptr(), B, C, H, W, bs, ps,
                                                  H * W * n * C, n * C, layout, None if bias is None else bias.data_ptr(),
                                                  _stream()), "split_planes")
     return out
@@ -413,6 +414,7 @@ def split_planes_colsum(t: torch.Tensor, layout: int = PLANES_HLH, dtype=torch.b
     """``split_planes(t, 0, ps, layout)`` of the WHOLE fp32 pixel-major tensor ``t`` (B, H, W, ps) and, from the same pass, the sum of
     ``t`` over all images and pixels (ps floats, fixed summation order): the module's backward needs dqkv both ways (three-plane
     rows for its GEMMs, column sums as the bias gradients) -- ccnet_cca_split_planes_colsum_f32."""
+    t, t_bs, t_ps = _pm_view("split_planes_colsum source", t, torch.float32)
     B, H, W, ps = t.shape
     n = 2 if layout == PLANES_HL else 3
     out = torch.empty((B, H, W, n, ps), device=t.device, dtype=dtype)
@@ -421,7 +423,7 @@ def split_planes_colsum(t: torch.Tensor, layout: int = PLANES_HLH, dtype=torch.b
     with torch.cuda.device(t.device):
         _ws, wsp, wsn = _workspace(lib.ccnet_cca_workspace_bytes(_lib.CCNET_WS_SPLIT_COLSUM, B, ps, 0, H, W), t.device)
         lib.check(lib.ccnet_cca_split_planes_colsum_f32(t.data_ptr(), out.data_ptr(), colsum.data_ptr(), wsp, wsn, B, ps, H, W,
-                                                        t.stride(0), t.stride(2), H * W * n * ps, n * ps, layout, _stream()),
+                                                        t_bs, t_ps, H * W * n * ps, n * ps, layout, _stream()),
                   "split_planes_colsum")
     return out, colsum
 
@@ -429,11 +431,14 @@ def split_planes_colsum(t: torch.Tensor, layout: int = PLANES_HLH, dtype=torch.b
 def nchw_to_planes(x: torch.Tensor, layout: int = PLANES_HL, dtype=torch.int16) -> torch.Tensor:
     """fp32 NCHW (B, C, H, W) -> planes (B, H, W, n, C) (transposed and split in one pass, csrc/cca_gmap.hpp)."""
     B, C, H, W = x.shape
+    # dense (C, H, W) images at any batch stride >= C H W (a channel slice of a wider tensor) are read in place
+    if x.stride()[1:] != (H * W, W, 1) or x.stride(0) < C * H * W:
+        x = x.contiguous()
     n = 2 if layout == PLANES_HL else 3
     out = torch.empty((B, H, W, n, C), device=x.device, dtype=dtype)
     lib = _lib.get_lib()
     with torch.cuda.device(x.device):
-        lib.check(lib.ccnet_cca_nchw_to_planes_f32(x.data_ptr(), out.data_ptr(), B, C, H, W, C * H * W, H * W * n * C, n * C,
+        lib.check(lib.ccnet_cca_nchw_to_planes_f32(x.data_ptr(), out.data_ptr(), B, C, H, W, x.stride(0), H * W * n * C, n * C,
                                                    layout, _stream()), "nchw_to_planes")
     return out
 

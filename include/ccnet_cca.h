@@ -201,6 +201,17 @@ int ccnet_cca_backward_strided_f32(const float *dy, const float *q, const float 
  * The attention tensor A (B, H, W, H+W), the scratch tensor, gamma, dgamma and every accumulation are fp32; products
  * of the bf16 features are exact on the matrix pipe; outputs are rounded to nearest even once, on store.
  * Constraints: max(H, W) <= 132, C % 8 == 0, Cq % 8 == 0, every bs / ps a multiple of 8, pointers 16-byte aligned.
+ * MEMORY CONTRACT of every view of the pixel-major and split-plane entry points, their producers and the projection GEMMs (q, k, v,
+ * x, y, dy, dq, dk, dv, v_planes, d3, GEMM operands with a row stride; enforced by tests/cca_cases.py on guarded buffers, in the
+ * emulator and on the device): the elements of a view are (b, p, c) with c below the channel count -- for planes, below planes * C.
+ *   - bytes outside a view are never written: not the gap after a pixel's channels (for the dq slice of a packed dq | dk | dv that
+ *     gap is dk and dv), not the gap between images, nothing past the last in-view element of the last image -- a batch stride may
+ *     be as tight as (H*W - 1) * ps + C and the allocation may end there;
+ *   - values outside a view never reach a result: whatever the gaps and the memory next to a view hold (NaN included), the results
+ *     are bit-identical to those of the same call on dense tensors -- a stride never changes a summation order;
+ *   - a workspace needs no initialisation and exactly ccnet_cca_workspace_bytes(...) bytes suffice (256-byte aligned, as every
+ *     allocator delivers); 256 bytes less return CCNET_E_WORKSPACE; ``scratch`` needs none either;
+ *   - input tensors are left bit-identical (``scratch`` is in-out; ``v_planes`` is an output of the forward that takes ``v``).
  * y = gamma * (column + row aggregation) + x       (functions.py:46-49)
  * ``workspace``: ccnet_cca_workspace_bytes(CCNET_WS_PM_FORWARD / _BACKWARD, ...) bytes (fp32 column partials; + softmax
  * partials; bf16 and fp32 views alike). */

@@ -11,80 +11,10 @@ import ctypes
 import numpy as np
 
 import abn_oracle as O
+from guarded_memory import GUARD, Buf, DeviceMemory, HostMemory  # noqa: F401  (the tests reach them through here)
 
-GUARD = 64                                   # guard elements on each side of every buffer
-_KINDS = {"f32": (4, np.uint32, 0xCDCDCDCD), "bf16": (2, np.uint16, 0xCDCD),
-          "f64": (8, np.uint64, 0x7FF8000000000000)}        # fp64 bands hold NaN
 TENSORS = ("x", "residual", "dy", "y", "dx", "dresidual")
 OFFSETS = {False: (1, 2, 3), True: (1, 3, 4)}        # elements past a 16-byte boundary: fp32 4/8/12 bytes, bf16 2/6/8 bytes
-
-
-class HostMemory:
-    """numpy arrays standing in for device memory (the emulator's back end)"""
-    name = "emu"
-    stream = None
-
-    def new(self, nbytes):
-        raw = np.empty(nbytes, np.uint8)
-        return raw, raw.ctypes.data
-
-    def upload(self, raw, at, data):
-        raw[at:at + data.size] = data
-
-    def download(self, raw):
-        return raw
-
-
-class DeviceMemory:
-    """torch byte tensors on the current device; copies and launches go on the current stream"""
-    name = "gpu"
-
-    def __init__(self):
-        import torch
-        self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device())
-
-    @property
-    def stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
-
-    def new(self, nbytes):
-        raw = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
-        return raw, raw.data_ptr()
-
-    def upload(self, raw, at, data):
-        raw[at:at + data.size].copy_(self.torch.from_numpy(np.ascontiguousarray(data)))
-
-    def download(self, raw):
-        return raw.cpu().numpy()
-
-
-class Buf:
-    """``n`` elements of ``kind`` starting ``offset`` elements past a 16-byte boundary, GUARD elements of a fixed bit pattern
-    on each side.  The offset is a whole number of elements and the data lie inside the allocation."""
-
-    def __init__(self, mem, name, kind, n, offset=0, data=None):
-        size, self.utype, pat = _KINDS[kind]
-        assert 0 <= offset * size < 16
-        self.mem, self.name, self.n, self.size = mem, name, n, size
-        total = 2 * GUARD * size + 32 + n * size
-        self.raw, base = mem.new(total)
-        self.start = GUARD * size + (-(base + GUARD * size)) % 16 + offset * size
-        assert self.start + n * size + GUARD * size <= total and (base + self.start) % size == 0
-        assert (base + self.start) % 16 == offset * size
-        self.ptr = base + self.start
-        # the pattern is laid from the data's first byte, so it is element-aligned on both sides
-        self.image = np.array([pat], self.utype).view(np.uint8)[(np.arange(total) - self.start) % size]
-        if data is not None:
-            self.image[self.start:self.start + n * size] = np.ascontiguousarray(data).view(np.uint8).ravel()
-        mem.upload(self.raw, 0, self.image)
-
-    def read(self, dtype):
-        """the data, and whether both guard bands still hold their pattern"""
-        got = np.asarray(self.mem.download(self.raw))
-        a, b = self.start, self.start + self.n * self.size
-        intact = np.array_equal(got[:a], self.image[:a]) and np.array_equal(got[b:], self.image[b:])
-        return got[a:b].copy().view(dtype), intact
 
 
 def run_abn(lib, mem, x, weight, bias, rm, rv, dy, training=True, act=0, p=0.01, gamma_mode=0, eps=1e-5, momentum=0.1,
