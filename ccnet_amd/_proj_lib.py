@@ -1,0 +1,106 @@
+"""ctypes binding of the C ABI declared in include/ccnet_proj.h (the module's bf16 projections on the library's own MFMA GEMM).
+
+The product loads ``ccnet_amd/csrc_proj/libccnet_proj.so`` (built for gfx950 by ``__graft_entry__.build()``), a library of its
+own beside the other five.  As with :mod:`ccnet_amd._lib` there is no fallback: a missing library raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import re
+from ctypes import c_char_p, c_int, c_long, c_size_t, c_void_p
+from typing import List, Optional, Tuple
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(_HERE, "csrc_proj")
+LIB_PATH = os.path.join(CSRC, "libccnet_proj.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ccnet_proj.h")
+
+CCNET_PROJ_VERSION = 100    # include/ccnet_proj.h
+CCNET_PROJ_E_BADSHAPE, CCNET_PROJ_E_NULLPTR, CCNET_PROJ_E_BADFLAGS, CCNET_PROJ_E_WORKSPACE = -1, -2, -3, -4
+CCNET_PROJ_BF16, CCNET_PROJ_F32 = 0, 1
+TILE_ROWS = 256             # rows of the GEMM's workgroup tile (csrc/cca_gemm.hpp PG_BM)
+MAX_ELEMS = 1 << 30         # bf16 elements whose byte offsets stay below 2^31
+
+_P = c_void_p  # every tensor argument is a raw device pointer
+
+# name -> (restype, argtypes); mirrors include/ccnet_proj.h one to one
+_PROTOTYPES = {
+    "ccnet_proj_version": (c_int, []),
+    "ccnet_proj_arch": (c_char_p, []),
+    "ccnet_proj_last_error": (c_char_p, []),
+    "ccnet_proj_gemm_bf16": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_long, c_long, c_long, c_long, _P]),
+    "ccnet_proj_pack": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P]),
+    "ccnet_proj_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ccnet_proj_colsum_bf16": (c_int, [_P, _P, c_int, c_int, c_long, _P, c_size_t, _P]),
+}
+
+
+def declared_symbols(header: str = HEADER_PATH) -> List[str]:
+    """Every function name include/ccnet_proj.h declares."""
+    with open(header) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(ccnet_\w+)\s*\(", text)))
+
+
+def gemm_contract_ok(N: int, K: int, lda: int, ldw: int, ldo: int, ldadd: Optional[int] = None) -> bool:
+    """The shape half of ``ccnet_proj_gemm_bf16``'s contract (the row count is the planner's business)."""
+    return (N > 0 and K > 0 and K % 8 == 0 and N % 4 == 0 and lda % 8 == 0 and ldw % 8 == 0 and ldo % 4 == 0
+            and lda >= K and ldw >= K and ldo >= N and N * ldw < MAX_ELEMS
+            and (ldadd is None or (ldadd % 4 == 0 and ldadd >= N)))
+
+
+def plan_rows(M: int, lda: int, ldo: int, ldadd: int = 0) -> List[Tuple[int, int]]:
+    """[(first row, rows)] of the launches that cover M rows: every launch but the last is a whole number of 256-row tiles, and
+    rows * stride < 2^30 elements for each of the three row-strided operands (every byte offset of a launch below 2^31).  An
+    empty list: not even one tile fits under the limit."""
+    widest = max(lda, ldo, ldadd)
+    if M <= 0 or widest <= 0:
+        return []
+    rows = (MAX_ELEMS - 1) // widest // TILE_ROWS * TILE_ROWS
+    if rows <= 0:
+        return []
+    return [(m0, min(rows, M - m0)) for m0 in range(0, M, rows)]
+
+
+class ProjError(RuntimeError):
+    pass
+
+
+class ProjLibrary:
+    """A loaded libccnet_proj.so (or, in the CPU tests, the emulator build of the same sources)."""
+
+    def __init__(self, path: str = LIB_PATH):
+        if not os.path.exists(path):
+            raise ProjError(
+                f"{path} not found: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()').  "
+                "ccnet_amd has no CPU or PyTorch fallback for the projection kernels.")
+        self.path = path
+        self.dll = ctypes.CDLL(path)
+        for name, (res, args) in _PROTOTYPES.items():
+            fn = getattr(self.dll, name)
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)
+        if self.ccnet_proj_version() != CCNET_PROJ_VERSION:
+            raise ProjError(f"{path} exports C ABI version {self.ccnet_proj_version()}, this binding is written against "
+                            f"{CCNET_PROJ_VERSION} (include/ccnet_proj.h): rebuild the extension")
+
+    def last_error(self) -> str:
+        return self.ccnet_proj_last_error().decode()
+
+    def check(self, code: int, what: str = "") -> None:
+        if code != 0:
+            raise ProjError(f"{what or 'ccnet_proj'} failed with code {code}: {self.last_error()}")
+
+
+_lib: Optional[ProjLibrary] = None
+
+
+def get_lib() -> ProjLibrary:
+    """The process-wide device library; raises ProjError when it has not been built."""
+    global _lib
+    if _lib is None:
+        import torch  # noqa: F401  (map PyTorch's HIP runtime first, as _lib.get_lib does)
+        _lib = ProjLibrary(LIB_PATH)
+    return _lib

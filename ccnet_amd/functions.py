@@ -25,7 +25,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 from torch.nn import Softmax
 
-from . import _lib
+from . import _lib, _proj_lib
 from ._lib import CCNET_CA_ENERGY, CCNET_CA_SOFTMAX
 
 __all__ = ["INF", "CA_Weight", "CA_Map", "CrissCrossFunction", "ca_weight", "ca_map", "ca_softmax",
@@ -304,6 +304,50 @@ def pm_bf16_covers(B, C, Cq, H, W):
     return pm_covers(torch.bfloat16, B, C, Cq, H, W)
 
 
+def _pm_core_forward(qkv, q_bs, q_ps, x, x_bs, x_ps, gamma, cq):
+    """(y, A) of the fused core on pixel-major views (``_pm_view`` results): ccnet_cca_forward_pm_bf16 / _f32 -- the call the
+    pixel-major nodes share"""
+    B, H, W, ct = qkv.shape
+    C = ct - 2 * cq
+    es, tag = _PM_DTYPES[qkv.dtype][0], _PM_DTYPES[qkv.dtype][3]
+    lib = _lib.get_lib()
+    y = torch.empty((B, H, W, C), device=x.device, dtype=qkv.dtype)
+    A = torch.empty((B, H, W, H + W), device=x.device, dtype=torch.float32)
+    _ws, ws_ptr, nbytes = _workspace(lib.ccnet_cca_pm_workspace_bytes(B, C, cq, H, W, 0), x.device)
+    p = qkv.data_ptr()
+    fwd = getattr(lib, "ccnet_cca_forward_pm_" + tag)
+    with torch.cuda.device(x.device):
+        lib.check(fwd(p, p + es * cq, p + 2 * es * cq, x.data_ptr(), gamma.data_ptr(), y.data_ptr(), A.data_ptr(),
+                      B, C, cq, H, W, q_bs, q_ps, q_bs, q_ps, q_bs, q_ps, x_bs, x_ps, H * W * C, C,
+                      ws_ptr, nbytes, _stream()), "cca_forward_pm_" + tag)
+    return y, A
+
+
+def _pm_core_backward(dy, dy_bs, dy_ps, qkv, A, gamma, cq):
+    """(dqkv packed like qkv, dgamma) of the fused core on pixel-major views: ccnet_cca_backward_pm_bf16 / _f32.  ``A`` None: the
+    attention is rebuilt by the forward's own affinity + softmax kernels, bit-identical to what a saving forward kept."""
+    lib = _lib.get_lib()
+    B, H, W, ct = qkv.shape
+    C = ct - 2 * cq
+    es, _, _, tag = _PM_DTYPES[qkv.dtype]
+    if A is None:
+        p = qkv.data_ptr()
+        A = _attention_pm(lib, p, p + es * cq, tag == "bf16", B, cq, H, W, qkv.stride(0), qkv.stride(2), qkv.device)
+    dqkv = torch.empty((B, H, W, ct), device=qkv.device, dtype=qkv.dtype)
+    dgamma = torch.empty_like(gamma)
+    scratch = torch.empty_like(A)
+    _ws, ws_ptr, nbytes = _workspace(lib.ccnet_cca_pm_workspace_bytes(B, C, cq, H, W, 1), qkv.device)
+    p, g = qkv.data_ptr(), dqkv.data_ptr()
+    bs, ps = qkv.stride(0), qkv.stride(2)
+    bwd = getattr(lib, "ccnet_cca_backward_pm_" + tag)
+    with torch.cuda.device(qkv.device):
+        lib.check(bwd(dy.data_ptr(), p, p + es * cq, p + 2 * es * cq, A.data_ptr(), gamma.data_ptr(),
+                      g, g + es * cq, g + 2 * es * cq, dgamma.data_ptr(), scratch.data_ptr(), B, C, cq, H, W,
+                      dy_bs, dy_ps, bs, ps, bs, ps, bs, ps, H * W * ct, ct, H * W * ct, ct, H * W * ct, ct,
+                      ws_ptr, nbytes, _stream()), "cca_backward_pm_" + tag)
+    return dqkv, dgamma
+
+
 class CrissCrossPMFunction(torch.autograd.Function):
     """Fused core on PIXEL-MAJOR features (csrc/cca_gmap.hpp; bf16 = BASELINE configs[4], fp32 = the small-batch path):
     ``qkv`` is the packed (B, H, W, 2*Cq + C) projection (query | key | value channel slices, functions.py:29-35
@@ -325,16 +369,7 @@ class CrissCrossPMFunction(torch.autograd.Function):
         if not pm_covers(qkv.dtype, B, C, cq, H, W):
             raise RuntimeError(f"pixel-major {tag} kernels cover strips <= {longest} and channel counts divisible by "
                                f"{_PM_DTYPES[qkv.dtype][1]}; got C = {C}, Cq = {cq}, H = {H}, W = {W}")
-        lib = _lib.get_lib()
-        y = torch.empty((B, H, W, C), device=x.device, dtype=qkv.dtype)
-        A = torch.empty((B, H, W, H + W), device=x.device, dtype=torch.float32)
-        _ws, ws_ptr, nbytes = _workspace(lib.ccnet_cca_pm_workspace_bytes(B, C, cq, H, W, 0), x.device)
-        p = qkv.data_ptr()
-        fwd = getattr(lib, "ccnet_cca_forward_pm_" + tag)
-        with torch.cuda.device(x.device):
-            lib.check(fwd(p, p + es * cq, p + 2 * es * cq, x.data_ptr(), gamma.data_ptr(), y.data_ptr(), A.data_ptr(),
-                          B, C, cq, H, W, q_bs, q_ps, q_bs, q_ps, q_bs, q_ps, x_bs, x_ps, H * W * C, C,
-                          ws_ptr, nbytes, _stream()), "cca_forward_pm_" + tag)
+        y, A = _pm_core_forward(qkv, q_bs, q_ps, x, x_bs, x_ps, gamma, cq)
         ctx.recompute = bool(recompute)
         ctx.save_for_backward(*((qkv, gamma) if ctx.recompute else (qkv, A, gamma)))
         ctx.cq = cq
@@ -344,32 +379,13 @@ class CrissCrossPMFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dy):
         cq = ctx.cq
-        lib = _lib.get_lib()
         if ctx.recompute:
-            # the attention rebuilt by the forward's own affinity + softmax kernels: bit-identical to what a saving forward kept
             qkv, gamma = ctx.saved_tensors
-            B, H, W, ct = qkv.shape
-            es, tag = _PM_DTYPES[qkv.dtype][0], _PM_DTYPES[qkv.dtype][3]
-            p = qkv.data_ptr()
-            A = _attention_pm(lib, p, p + es * cq, tag == "bf16", B, cq, H, W, qkv.stride(0), qkv.stride(2), qkv.device)
+            A = None
         else:
             qkv, A, gamma = ctx.saved_tensors
         dy, dy_bs, dy_ps = _pm_view("grad_output", dy, qkv.dtype)
-        B, H, W, ct = qkv.shape
-        C = ct - 2 * cq
-        es, _, _, tag = _PM_DTYPES[qkv.dtype]
-        dqkv = torch.empty((B, H, W, ct), device=qkv.device, dtype=qkv.dtype)
-        dgamma = torch.empty_like(gamma)
-        scratch = torch.empty_like(A)
-        _ws, ws_ptr, nbytes = _workspace(lib.ccnet_cca_pm_workspace_bytes(B, C, cq, H, W, 1), qkv.device)
-        p, g = qkv.data_ptr(), dqkv.data_ptr()
-        bs, ps = qkv.stride(0), qkv.stride(2)
-        bwd = getattr(lib, "ccnet_cca_backward_pm_" + tag)
-        with torch.cuda.device(qkv.device):
-            lib.check(bwd(dy.data_ptr(), p, p + es * cq, p + 2 * es * cq, A.data_ptr(), gamma.data_ptr(),
-                          g, g + es * cq, g + 2 * es * cq, dgamma.data_ptr(), scratch.data_ptr(), B, C, cq, H, W,
-                          dy_bs, dy_ps, bs, ps, bs, ps, bs, ps, H * W * ct, ct, H * W * ct, ct, H * W * ct, ct,
-                          ws_ptr, nbytes, _stream()), "cca_backward_pm_" + tag)
+        dqkv, dgamma = _pm_core_backward(dy, dy_bs, dy_ps, qkv, A, gamma, cq)
         return dqkv, dy, dgamma.view_as(gamma), None, None
 
 
@@ -553,6 +569,150 @@ def _projection_wgrad_gemm(lib, d, x):
                       "projection_wgrad_bf16")
             s0 += S
     return part.sum(0) if part.shape[0] > 1 else part[0]
+
+
+# ----------------------------------------------------------------------------------------------
+# the bf16 module node: projections on the library's own bf16 MFMA GEMM (csrc_proj/, include/ccnet_proj.h)
+# ----------------------------------------------------------------------------------------------
+_PROJ_PARAM_DTYPES = {torch.bfloat16: _proj_lib.CCNET_PROJ_BF16, torch.float32: _proj_lib.CCNET_PROJ_F32}
+
+
+def _proj_pack(wq, bq, wk, bk, wv, bv):
+    """(w (N, C) bf16, wt (C, N) bf16, b (N) fp32): the stacked weight, its transpose and the stacked bias from the CURRENT values
+    of the six parameters (bf16, or fp32 rounded to nearest even) by one launch, ``ccnet_proj_pack``.  No cache, for the reason
+    given at ``_pack_projection``."""
+    cq, C = wq.shape[0], wq.shape[1]
+    n = 2 * cq + C
+    dev = wq.device
+    ps = [t.detach() if t.is_contiguous() else t.detach().contiguous() for t in (wq, bq, wk, bk, wv, bv)]
+    if wq.dtype not in _PROJ_PARAM_DTYPES or any(t.dtype != wq.dtype or t.device != dev for t in ps):
+        raise RuntimeError("the bf16 module node needs six bf16 or six fp32 parameters on one device")
+    w = torch.empty((n, C), device=dev, dtype=torch.bfloat16)
+    wt = torch.empty((C, n), device=dev, dtype=torch.bfloat16)
+    b = torch.empty((n,), device=dev, dtype=torch.float32)
+    lib = _proj_lib.get_lib()
+    with torch.cuda.device(dev):
+        lib.check(lib.ccnet_proj_pack(*(t.data_ptr() for t in ps), _PROJ_PARAM_DTYPES[wq.dtype], w.data_ptr(), wt.data_ptr(),
+                                      b.data_ptr(), C, cq, _stream()), "proj_pack")
+    return w, wt, b
+
+
+def _proj_gemm(a, wt, bias=None, add=None):
+    """``bf16(a @ wt.T + bias + add)``, fp32 accumulation from bias + addend on, one rounding, by ``ccnet_proj_gemm_bf16``: ``a``
+    (M, K), ``wt`` (N, K), ``add`` (M, N) bf16 with contiguous rows at a row stride, ``bias`` (N) fp32 -> (M, N) bf16.  Row counts
+    beyond the entry point's 31-bit byte offsets run as several launches over whole 256-row tiles.  A shape outside the contract
+    raises: there is no other GEMM behind this one."""
+    M, K = a.shape
+    N = wt.shape[0]
+    ldadd = None if add is None else add.stride(0)
+    if (a.stride(1) != 1 or wt.stride(1) != 1 or (add is not None and add.stride(1) != 1)
+            or not _proj_lib.gemm_contract_ok(N, K, a.stride(0), wt.stride(0), N, ldadd)):
+        raise RuntimeError(f"ccnet_proj_gemm_bf16 does not take M, N, K = {M}, {N}, {K} at row strides {a.stride(0)}, {wt.stride(0)}, {ldadd}")
+    plan = _proj_lib.plan_rows(M, a.stride(0), N, ldadd or 0)
+    if not plan:
+        raise RuntimeError("ccnet_proj_gemm_bf16: one 256-row tile exceeds 31-bit byte offsets")
+    out = torch.empty((M, N), device=a.device, dtype=torch.bfloat16)
+    lib = _proj_lib.get_lib()
+    with torch.cuda.device(a.device):
+        for m0, m in plan:
+            lib.check(lib.ccnet_proj_gemm_bf16(a.data_ptr() + 2 * m0 * a.stride(0), wt.data_ptr(), None if bias is None else bias.data_ptr(),
+                                               None if add is None else add.data_ptr() + 2 * m0 * ldadd, out.data_ptr() + 2 * m0 * N,
+                                               m, N, K, a.stride(0), wt.stride(0), ldadd or 0, N, _stream()), "proj_gemm_bf16")
+    return out
+
+
+def _proj_colsum(d):
+    """``d.sum(0)`` of bf16 rows (M, N) as fp32 by ``ccnet_proj_colsum_bf16``: double accumulation in a fixed order (slab partials,
+    then one finishing workgroup), bit-identical run to run.  Row ranges beyond 31-bit byte offsets are summed range by range."""
+    M, N = d.shape
+    if d.stride(1) != 1 or N % 4 or d.stride(0) % 4:
+        raise RuntimeError(f"ccnet_proj_colsum_bf16 does not take N = {N} at row stride {d.stride(0)}")
+    plan = _proj_lib.plan_rows(M, d.stride(0), 0)
+    if not plan:
+        raise RuntimeError("ccnet_proj_colsum_bf16: one 256-row tile exceeds 31-bit byte offsets")
+    lib = _proj_lib.get_lib()
+    out = torch.empty((len(plan), N), device=d.device, dtype=torch.float32)
+    with torch.cuda.device(d.device):
+        for i, (m0, m) in enumerate(plan):
+            nbytes = lib.ccnet_proj_colsum_workspace_bytes(m, N)
+            ws = torch.empty(nbytes // 8, device=d.device, dtype=torch.float64)
+            lib.check(lib.ccnet_proj_colsum_bf16(d.data_ptr() + 2 * m0 * d.stride(0), out.data_ptr() + 4 * i * N, m, N, d.stride(0),
+                                                 ws.data_ptr(), nbytes, _stream()), "proj_colsum_bf16")
+    return out[0] if len(plan) == 1 else out.double().sum(0).float()
+
+
+def proj_bf16_covers(B, C, Cq, H, W):
+    """the contracts of the three GEMMs of the bf16 module node (forward, dx: ``ccnet_proj_gemm_bf16``; dW:
+    ``ccnet_cca_projection_wgrad_bf16``) and of the column sums, for contiguous pixel-major operands"""
+    n = 2 * Cq + C
+    return (_proj_lib.gemm_contract_ok(n, C, C, C, n) and _proj_lib.gemm_contract_ok(C, n, n, n, C, C) and n % 8 == 0 and C % 8 == 0
+            and bool(_proj_lib.plan_rows(B * H * W, n, n, C)))
+
+
+class CrissCrossPMBF16ModuleFunction(torch.autograd.Function):
+    """The whole module as ONE autograd node on bf16 PIXEL-MAJOR activations (BASELINE configs[4]) with its three projection GEMMs
+    on the library's own kernels: ``x`` (B, H, W, C) bf16, the six parameters bf16 or fp32 (what autocast keeps; rounded to bf16
+    for the GEMMs), ``gamma`` fp32; returns y (B, H, W, C) bf16.
+
+    Forward: ``ccnet_proj_pack`` (stacked weight, its transpose, stacked bias), ``ccnet_proj_gemm_bf16`` (q | k | v =
+    bf16(x W^T + b), the bias starting the accumulators), then the fused core exactly as ``CrissCrossPMBF16Function`` runs it.
+    Backward: the core's backward (dqkv), ONE GEMM dx = bf16(dy + dqkv W) with the residual gradient dy as the addend, dW = dqkv^T x by
+    ``ccnet_cca_projection_wgrad_bf16`` (fp32 partials added in a fixed order), db = the column sums of dqkv
+    (``ccnet_proj_colsum_bf16``).  Weight and bias gradients come back in each parameter's dtype: fp32 parameters get the fp32
+    sums unrounded.  Kept for the backward: x, qkv, both packed weights, gamma and -- unless ``recompute`` -- the attention.
+    No host synchronisation; every launch is on the current stream (capturable)."""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, gamma, recompute=False):
+        x, x_bs, x_ps = _pm_view("x", x, torch.bfloat16)
+        if not x.is_contiguous():                                            # (the GEMM's rows follow each other at one stride)
+            x = x.contiguous()
+            x_bs, x_ps = x.stride(0), x.stride(2)
+        gamma = _dev_f32("gamma", gamma)
+        B, H, W, C = x.shape
+        cq = wq.shape[0]
+        ct = 2 * cq + C
+        if tuple(wq.shape[:2]) != (cq, C) or tuple(wk.shape[:2]) != (cq, C) or tuple(wv.shape[:2]) != (C, C):
+            raise RuntimeError(f"projection weights do not fit x: {tuple(wq.shape)}, {tuple(wk.shape)}, {tuple(wv.shape)}, C = {C}")
+        if not (pm_bf16_covers(B, C, cq, H, W) and proj_bf16_covers(B, C, cq, H, W)):
+            raise RuntimeError(f"the bf16 module node covers strips <= 132 and C, C/8 divisible by 8; got C = {C}, Cq = {cq}, H = {H}, W = {W}")
+        _same_device(x, wq, gamma)
+        w, wt, b = _proj_pack(wq, bq, wk, bk, wv, bv)                      # (the current parameter values, every call: no cache)
+        qkv = _proj_gemm(x.view(B * H * W, C), w, b).view(B, H, W, ct)
+        y, A = _pm_core_forward(qkv, H * W * ct, ct, x, x_bs, x_ps, gamma, cq)
+        if not any(ctx.needs_input_grad):
+            return y
+        ctx.recompute = bool(recompute)
+        # (both packed weights -- the values this forward saw -- go through save_for_backward like every other kept tensor:
+        #  saved-tensor hooks / offload apply to them)
+        ctx.save_for_backward(*((x, qkv, gamma, w, wt) + (() if ctx.recompute else (A,))))
+        ctx.cq, ctx.param_dtype, ctx.shapes = cq, wq.dtype, (wq.shape, wk.shape, wv.shape)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        cq = ctx.cq
+        x, qkv, gamma, w, wt = ctx.saved_tensors[:5]
+        A = None if ctx.recompute else ctx.saved_tensors[5]
+        B, H, W, C = x.shape
+        M, ct = B * H * W, 2 * cq + C
+        dy, dy_bs, dy_ps = _pm_view("grad_output", dy, torch.bfloat16)
+        if dy_bs != H * W * dy_ps:                                           # (the addend's rows follow each other at one stride)
+            dy = dy.contiguous()
+            dy_bs, dy_ps = H * W * C, C
+        dqkv, dgamma = _pm_core_backward(dy, dy_bs, dy_ps, qkv, A, gamma, cq)
+        d2 = dqkv.view(M, ct)
+        # dx = bf16(dy + dqkv W): one GEMM, the core's residual gradient starting its accumulators (no separate add)
+        dx = _proj_gemm(d2, wt, None, dy.as_strided((M, C), (dy_ps, 1))).view(B, H, W, C)
+        dw = _projection_wgrad_gemm(_lib.get_lib(), d2, x.view(M, C))       # (ct, C) fp32: S partials added in a fixed order
+        if dw is None:
+            raise RuntimeError("ccnet_cca_projection_wgrad_bf16 does not take this shape")
+        db = _proj_colsum(d2)
+        dt = ctx.param_dtype
+        sq, sk, sv = ctx.shapes
+        return (dx, dw[:cq].to(dt).reshape(sq), db[:cq].to(dt), dw[cq:2 * cq].to(dt).reshape(sk), db[cq:2 * cq].to(dt),
+                dw[2 * cq:].to(dt).reshape(sv), db[2 * cq:].to(dt), dgamma.view_as(gamma), None)
 
 
 class CrissCrossPlanesModuleFunction(torch.autograd.Function):
@@ -759,10 +919,16 @@ class CrissCrossAttention(nn.Module):
     #: run the blocked fp32 plane kernels on fp32 copies (route ``f32-planes-cast``), anything else the strip family through fp32
     #: copies (route ``separate-strips``).
     native_bf16 = True
+    #: bf16 inputs on the pixel-major kernels: run the three projection GEMMs on the library's own bf16 MFMA kernels as well (route
+    #: ``bf16-pixel-major-lib``, ``CrissCrossPMBF16ModuleFunction``: the whole module one autograd node, bias and residual gradient
+    #: in the accumulators, no ``torch.cat`` of the parameters and no separate gradient add) instead of stock ``F.linear`` and its
+    #: autograd.  Opt-in (DESIGN.md 15 has the measurement).
+    library_bf16_projections = False
 
     #: route name -> what runs (``route(x)`` picks one; ``forward`` only dispatches on it)
     ROUTES = {
         "bf16-pixel-major": "one x^T W^T projection + pixel-major bf16 MFMA kernels (BASELINE configs[4])",
+        "bf16-pixel-major-lib": "library_bf16_projections: one autograd node, the projections on the library's bf16 MFMA GEMM + the same pixel-major kernels",
         "f32-planes": "one autograd node: projection GEMM, v / dy as bf16 hi | lo planes, NCHW x / y / dy (channels_last inputs: one copy)",
         "f32-planes-cast": "fp32 inputs under autocast, fp16 inputs, bf16 inputs beyond the bf16 kernels' 132 positions: the f32-planes node on fp32 copies, autocast off inside",
         "separate-strips": "three convolutions + NCHW strip / windowed / any-shape kernels (functions.py:29-35 as written): every other input",
@@ -784,6 +950,8 @@ class CrissCrossAttention(nn.Module):
         if x.dtype == torch.bfloat16 and self.native_bf16:
             if (fast_ok and (self._fusable(x) or (torch.is_autocast_enabled() and self._fusable()))   # (autocast casts W for linear)
                     and pm_bf16_covers(B, C, cq, H, W)):
+                if self.library_bf16_projections and self._library_projections_ok(x, B, C, cq, H, W):
+                    return "bf16-pixel-major-lib"
                 return "bf16-pixel-major"
         if x.dtype == torch.float32 and not torch.is_autocast_enabled() and self._fusable(x):
             # (strips beyond 132 positions -- rows, columns or both, up to 528 -- run in blocks.  Round 3 ran a TALL map whose width
@@ -822,6 +990,10 @@ class CrissCrossAttention(nn.Module):
             qkv = torch.nn.functional.linear(xp, self._stacked_weight().flatten(1), self._stacked_bias()).to(torch.bfloat16)
             y = CrissCrossPMBF16Function.apply(qkv, xp, self.gamma.float(), cq, self.recompute_attention).permute(0, 3, 1, 2)
             return y if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous() else y.contiguous()
+        if r == "bf16-pixel-major-lib":
+            y = CrissCrossPMBF16ModuleFunction.apply(x.permute(0, 2, 3, 1), *params, self.gamma.float(),
+                                                     self.recompute_attention).permute(0, 3, 1, 2)
+            return y if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous() else y.contiguous()
         if r == "f32-planes":
             split_gemm = self.split_bf16_projections and x.shape[0] * x.shape[2] * x.shape[3] >= self.split_bf16_min_pixels
             y = CrissCrossPlanesModuleFunction.apply(x.contiguous(), *params, self.gamma, split_gemm, self.recompute_attention)
@@ -840,6 +1012,14 @@ class CrissCrossAttention(nn.Module):
         out = CrissCrossFunction.apply(proj_query.float(), proj_key.float(), proj_value.float(),
                                        x.float(), self.gamma.float(), self.recompute_attention)
         return out.to(x.dtype)
+
+    def _library_projections_ok(self, x, B, C, cq, H, W):
+        """``ccnet_proj_gemm_bf16``'s contract for this input, and parameters it packs: bf16, or fp32 under a bf16 autocast"""
+        w = self.query_conv.weight
+        if w.device != x.device or not proj_bf16_covers(B, C, cq, H, W):
+            return False
+        return w.dtype == torch.bfloat16 or (w.dtype == torch.float32 and torch.is_autocast_enabled()
+                                             and torch.get_autocast_gpu_dtype() == torch.bfloat16)
 
     def _stacked_weight(self):
         return torch.cat([self.query_conv.weight, self.key_conv.weight, self.value_conv.weight], 0)

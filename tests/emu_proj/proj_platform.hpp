@@ -1,0 +1,25 @@
+// proj_platform.hpp (tests/emu_proj) -- SIMT-emulator twins of ccnet_amd/csrc_proj/proj_platform.hpp.  Test infrastructure only:
+// the emulator build puts tests/emu and this directory FIRST on the include path; the product build never does.
+#pragma once
+#include <cca_platform.hpp>
+
+namespace proj {
+
+typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
+
+__device__ inline u32x2v fbuf_load_x2(const cca::FBuf &b, int voff_bytes, int soff_bytes) {
+    u32x2v v;
+    for (int e = 0; e < 2; ++e) {
+        const float f = cca::fbuf_load(b, voff_bytes + 4 * e, soff_bytes);
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        v[e] = u;
+    }
+    return v;
+}
+
+__device__ inline void lds_wait_all(cca::u32x4 (&)[4], cca::u32x4 (&)[4]) {}
+
+}  // namespace proj
+
+#define PROJ_LAUNCH(kern, grid, block, stream, ...) emu::launch((grid), (block), [&]() { kern(__VA_ARGS__); })
