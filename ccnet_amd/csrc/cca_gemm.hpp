@@ -158,8 +158,8 @@ __global__ __launch_bounds__(PG_THREADS, 1) void proj_gemm_kernel(const ProjGemm
     }
     u32x4 b0[4], a0[4], b1[4], a1[4];
     read(b0, a0, 0, 0);
-    int slot = 0;
-    for (int it = 0; it < nk; ++it) {
+    int slot = 0, it = 0;
+    do {                                            // (nk >= 1: K > 0 is an argument check; no path skips the loop with reads in flight)
         const int next = slot == PG_NBUF - 1 ? 0 : slot + 1;
         read(b1, a1, slot, 1);
         lds_wait_keep<8>(b0, a0);                  // the first half's fragments are here, the second half's on their way
@@ -170,14 +170,17 @@ __global__ __launch_bounds__(PG_THREADS, 1) void proj_gemm_kernel(const ProjGemm
             for (int j = 0; j < 4; ++j) acc[t][j] = mfma_bf16_16x16x32(b0[j], a0[t], acc[t][j]);
         sched_fence();
         const bool fill = it + 3 < nk;
+        // the second half's fragments are here: a wait for ALL reads, on every path and BEFORE the branch (the barrier below
+        // waits for lgkmcnt(0) anyway, so this costs the steps that take it nothing, and the last step needs exactly it) -- what
+        // holds b1 / a1 must not depend on a later branch agreeing with the loop condition (cca_platform.hpp, lds_wait_keep)
+        lds_wait_keep<0>(b1, a1);
         if (it + 1 < nk) {
             // stage it + 1 landed and every wavefront holds stage `it` in registers: its slot takes stage it + 3 at once; the
             // fill of stage it + 2 (this wavefront's newest vector-memory operations) stays in flight
             if (it + 2 < nk) barrier_dma_keep<PG_NPW>();
             else             barrier_dma_keep<0>();
+            read(b0, a0, next, 0);                  // (the last step requests nothing: there is no next stage)
         }
-        read(b0, a0, next, 0);                      // (after the last stage: eight reads of a dead slot that nobody uses)
-        lds_wait_keep<8>(b1, a1);
         sched_fence();
         // second half; the fill instructions of stage it + 3 ride in the shadow of its first MFMAs
 #pragma unroll
@@ -192,7 +195,8 @@ __global__ __launch_bounds__(PG_THREADS, 1) void proj_gemm_kernel(const ProjGemm
             }
         sched_fence();
         slot = next;
-    }
+    } while (++it < nk);
+    lds_wait_keep<0>(b0, a0);                       // nothing is outstanding after the loop: the epilogue may touch any register
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int m = m0 + wm * 64 + 16 * t + ln;

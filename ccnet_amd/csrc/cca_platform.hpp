@@ -130,8 +130,20 @@ __device__ __forceinline__ void fbuf_load_to_lds_x4_uncounted(const FBuf &b, flo
 // LDS reads outside the compiler's lgkmcnt bookkeeping, for a register ping-pong (cca_gemm.hpp): across a loop back edge hipcc
 // waits with lgkmcnt(0) before the first use of ANY tracked read -- also for the reads of the NEXT half step requested just
 // before, which are the ones the MFMAs are supposed to hide.  The kernel waits itself: lds_wait_keep<N>() returns once at
-// most N of this wave's LDS reads are outstanding (they return in order) and carries the fragment registers as operands,
-// so no use of them can be scheduled above it.
+// most N of this wave's LDS reads are outstanding (they return in order).
+//
+// What holds, and what does not.  To the compiler the read's result is available as soon as the asm statement has been
+// issued: nothing -- not the compiler, not the hardware -- keeps an instruction from touching the destination registers while
+// the read is in flight.  The wait is TWO statements: the s_waitcnt itself without operands (volatile asm statements keep their
+// order, so it stays behind the volatile reads and needs no register shuffling in front of it), then an empty statement that
+// carries the fragment registers as tied operands: uses of the values it "produces" come after it, and a copy the register
+// allocator makes for the tied operands lands behind the real wait.  (With the registers tied to the s_waitcnt itself hipcc
+// placed such copies ABOVE it: reads of registers still in flight.)  That orders the uses the SOURCE makes after the wait.  It
+// does not order what the compiler does with the registers on its own between a read and its wait (copies at a join, reuse of
+// a register it believes dead), so the rule for callers is: every path from a read to any other mention of its registers, or
+// to the end of their life, passes a wait that names them -- without relying on two branch conditions agreeing -- and the
+// instruction stream is checked: tests/test_isa_hazards.py walks the assembly of every kernel for an instruction that touches
+// the destination of a read that may be in flight.
 template <int OFF>
 __device__ __forceinline__ u32x4 lds_read_x4_uncounted(const void *p) {
     const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
@@ -141,9 +153,8 @@ __device__ __forceinline__ u32x4 lds_read_x4_uncounted(const void *p) {
 }
 template <int KEEP>
 __device__ __forceinline__ void lds_wait_keep(u32x4 (&b)[4], u32x4 (&a)[4]) {
-    asm volatile("s_waitcnt lgkmcnt(%8)"
-                 : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])
-                 : "n"(KEEP) : "memory");
+    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(KEEP) : "memory");
+    asm volatile("" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])::"memory");
 }
 
 // Workgroup barrier that orders LDS traffic only: waits for this wave's LDS operations (lgkmcnt) but NOT for

@@ -16,10 +16,11 @@
 // groups of a wavefront four neighbouring 8-byte columns, i.e. every row of a wavefront's 64 x 64 tile goes out as four 32-byte
 // pieces.  (A lane exchange that would build 16-byte stores was not measured; the epilogue is 1/nk of the kernel.)
 //
-// Two differences from proj_gemm_kernel's loop: the last k step does not request the fragments of a stage that does not exist
-// (there: eight reads of a dead slot whose registers the epilogue then reuses while the reads are still in flight), and the
-// second half of the last step waits for ALL of the wavefront's uncounted LDS reads -- after the loop none is outstanding, so
-// the epilogue may touch any register.
+// The loop is proj_gemm_kernel's, waits included (cca_platform.hpp, lds_wait_keep: the reads are outside the compiler's
+// bookkeeping, so every path from a read to another mention of its registers passes a wait that names them): the second half's
+// fragments are waited for with lgkmcnt(0) BEFORE the branch on "is there a next stage", the last k step requests nothing, and a
+// wait after the loop names the first half's registers -- the epilogue may touch any register.  tests/test_isa_hazards.py
+// checks the instruction stream for it.
 //
 // One launch form serves the forward (A = x, K = C, N = 2 Cq + C, bias) and the adjoint with respect to the input (A = dqkv,
 // K = 2 Cq + C, N = C, Wt = the transposed stacked weight, add = the residual gradient).  At (16,512,129,129) both are bound by
@@ -164,8 +165,8 @@ __global__ __launch_bounds__(PG_THREADS, 1) void gemm_bf16_kernel(const GemmJob 
     }
     u32x4 b0[4], a0[4], b1[4], a1[4];
     read(b0, a0, 0, 0);
-    int slot = 0;
-    for (int it = 0; it < nk; ++it) {
+    int slot = 0, it = 0;
+    do {                                            // (nk >= 1: K > 0 is an argument check; no path skips the loop with reads in flight)
         const int next = slot == PG_NBUF - 1 ? 0 : slot + 1;
         const bool more = it + 1 < nk;
         read(b1, a1, slot, 1);
@@ -177,15 +178,15 @@ __global__ __launch_bounds__(PG_THREADS, 1) void gemm_bf16_kernel(const GemmJob 
             for (int j = 0; j < 4; ++j) acc[t][j] = cca::mfma_bf16_16x16x32(b0[j], a0[t], acc[t][j]);
         cca::sched_fence();
         const bool fill = it + 3 < nk;
+        // the second half's fragments are here: a wait for ALL reads, on every path and before the branch (the barrier below waits
+        // for lgkmcnt(0) anyway; the last step needs exactly it)
+        cca::lds_wait_keep<0>(b1, a1);
         if (more) {
             // stage it + 1 landed and every wavefront holds stage `it` in registers: its slot takes stage it + 3 at once; the
             // fill of stage it + 2 (this wavefront's newest vector-memory operations) stays in flight
             if (it + 2 < nk) cca::barrier_dma_keep<PG_NPW>();
             else             cca::barrier_dma_keep<0>();
-            read(b0, a0, next, 0);
-            cca::lds_wait_keep<8>(b1, a1);
-        } else {
-            lds_wait_all(b1, a1);                   // the last step: nothing more is requested, nothing stays outstanding
+            read(b0, a0, next, 0);                  // (the last step requests nothing: there is no next stage)
         }
         cca::sched_fence();
         // second half; the fill instructions of stage it + 3 ride in the shadow of its first MFMAs
@@ -201,7 +202,8 @@ __global__ __launch_bounds__(PG_THREADS, 1) void gemm_bf16_kernel(const GemmJob 
             }
         cca::sched_fence();
         slot = next;
-    }
+    } while (++it < nk);
+    cca::lds_wait_keep<0>(b0, a0);                  // nothing is outstanding after the loop: the epilogue may touch any register
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int m = m0 + wm * 64 + 16 * t + ln;

@@ -13,10 +13,6 @@ __device__ __forceinline__ u32x2v fbuf_load_x2(const cca::FBuf &b, int voff_byte
     return __builtin_bit_cast(u32x2v, __builtin_amdgcn_raw_buffer_load_b64(b, voff_bytes, soff_bytes, 0));
 }
 
-// every uncounted LDS read of this wave (cca::lds_read_x4_uncounted) has returned; the fragment registers ride along as operands
-// so that no use of them is scheduled above the wait
-__device__ __forceinline__ void lds_wait_all(cca::u32x4 (&b)[4], cca::u32x4 (&a)[4]) { cca::lds_wait_keep<0>(b, a); }
-
 }  // namespace proj
 
 #define PROJ_LAUNCH(kern, grid, block, stream, ...)                                        \

@@ -470,9 +470,11 @@ def check_pack_projection(lib, r, C, split):
 # projection GEMMs.  Operands are (rows, cols) matrices with a row stride: View(B = 1, P = rows, C = cols)
 # ---------------------------------------------------------------------------------------------------------------------
 def _matrix(ar, name, kind, rows, cols, data, al, batches=1):
+    """(a width that is no multiple of the alignment unit -- an odd N -- keeps the smallest stride the entry points accept in the
+    dense form, up(cols, al): the elements between cols and the stride are gap, NaN before and after)"""
     if ar.form == "packed":                       # a column slice at an offset of wider rows
-        return ar.view(name, kind, batches, rows, cols, data, al, lead=al, wide=cols + 2 * al)
-    return ar.view(name, kind, batches, rows, cols, data, al)
+        return ar.view(name, kind, batches, rows, cols, data, al, lead=al, wide=up(cols, al) + 2 * al)
+    return ar.view(name, kind, batches, rows, cols, data, al, ps=up(cols, al) if ar.form == "dense" else None)
 
 
 def _gemm_inputs(seed, *shapes):
@@ -480,19 +482,53 @@ def _gemm_inputs(seed, *shapes):
     return [bf16_bits(rng.standard_normal(s, dtype=np.float32)) for s in shapes]
 
 
+def _projection_calls(lib, mem, form, guarded, M, N, K, a_, w_, biases):
+    """ccnet_cca_projection_bf16 on one pair of operands, once per entry of ``biases`` {output name: fp32 values or None}"""
+    ar = Arena(mem, form, guarded)
+    a, w = _matrix(ar, "a", "bf16", M, K, a_, 8), _matrix(ar, "wt", "bf16", N, K, w_, 8)
+    got = {}
+    for name, bias_ in biases.items():
+        bias = None if bias_ is None else ar.flat("bias_" + name, "f32", N, f32_bits(bias_))
+        out = _matrix(ar, name, "f32", M, N, None, 4)
+        lib.check(lib.ccnet_cca_projection_bf16(a.ptr, w.ptr, None if bias is None else bias.ptr, out.ptr, M, N, K, a.ps, w.ps, out.ps,
+                                                mem.stream), "projection_bf16")
+        ar.settle(f"projection_bf16({name})", (out,))
+        got[name] = ar.get(out)
+    return got
+
+
 def run_projection(lib, mem, form, guarded, zero, mnk):
     M, N, K = mnk
     a_, w_ = _gemm_inputs(M + N + K, (1, M, K), (1, N, K))
     bias_ = np.random.default_rng(K).standard_normal(N, dtype=np.float32)
-    ar = Arena(mem, form, guarded)
-    a, w = _matrix(ar, "a", "bf16", M, K, a_, 8), _matrix(ar, "wt", "bf16", N, K, w_, 8)
-    bias = ar.flat("bias", "f32", N, f32_bits(bias_))
-    out, out0 = _matrix(ar, "out", "f32", M, N, None, 4), _matrix(ar, "out_nobias", "f32", M, N, None, 4)
-    lib.check(lib.ccnet_cca_projection_bf16(a.ptr, w.ptr, bias.ptr, out.ptr, M, N, K, a.ps, w.ps, out.ps, mem.stream), "projection_bf16")
-    ar.settle("projection_bf16", (out,))
-    lib.check(lib.ccnet_cca_projection_bf16(a.ptr, w.ptr, None, out0.ptr, M, N, K, a.ps, w.ps, out0.ps, mem.stream), "projection_bf16")
-    ar.settle("projection_bf16(no bias)", (out0,))
-    return {"out": ar.get(out), "out_nobias": ar.get(out0)}
+    return _projection_calls(lib, mem, form, guarded, M, N, K, a_, w_, {"out": bias_, "out_nobias": None})
+
+
+def run_projection_placement(lib, mem, form, guarded, zero, mnk):
+    """Wt = the first N rows of the K x K identity, no bias: out is A[:, :N] widened to fp32, bit for bit, in every form (every
+    product but one per output is an exact zero).  The columns from the last 32 k of the range come from the last half k step."""
+    M, N, K = mnk
+    assert N <= K
+    a_, = _gemm_inputs(7 * M + N + K, (1, M, K))
+    r = _projection_calls(lib, mem, form, guarded, M, N, K, a_, bf16_bits(np.eye(K, dtype=np.float32)[None, :N]), {"out": None})
+    want = f32_bits(bf16_vals(a_[:, :, :N]))
+    assert np.array_equal(r["out"], want), ("placement", mnk, form, np.argwhere(r["out"] != want)[:4].tolist())
+    return r
+
+
+def run_projection_epilogue(lib, mem, form, guarded, zero, mnk):
+    """A = 0: out is the fp32 bias, bit for bit, in every form"""
+    M, N, K = mnk
+    w_, = _gemm_inputs(11 * M + 3 * N + K, (1, N, K))
+    bias_ = np.random.default_rng(K + 1).standard_normal(N, dtype=np.float32)
+    r = _projection_calls(lib, mem, form, guarded, M, N, K, np.zeros((1, M, K), np.uint16), w_, {"out": bias_})
+    want = np.broadcast_to(f32_bits(bias_), (1, M, N))
+    assert np.array_equal(r["out"], want), ("epilogue", mnk, form, np.argwhere(r["out"] != want)[:4].tolist())
+    return r
+
+
+def check_in_run(lib, r, *args):
+    """the bit-exact forms hold their expectation inside the runner, in every view form and on plain buffers"""
 
 
 def _within(got, ref, mag):
@@ -525,6 +561,22 @@ def run_adjoint(lib, mem, form, guarded, zero, bcpk):
     return {"dx": ar.get(dx), "dx_noadd": ar.get(dx0)}
 
 
+def run_adjoint_zero(lib, mem, form, guarded, zero, bcpk):
+    """d = 0: dx is the addend, bit for bit, in every form"""
+    B, C, P, K = bcpk
+    w_, = _gemm_inputs(B + C + P + K, (1, C, K))
+    add_ = np.random.default_rng(P + 1).standard_normal((B, C, P), dtype=np.float32)
+    ar = Arena(mem, form, guarded)
+    w, d = _matrix(ar, "w", "bf16", C, K, w_, 8), _matrix(ar, "d", "bf16", P, K, np.zeros((B, P, K), np.uint16), 8, batches=B)
+    add, dx = ar.flat("add", "f32", B * C * P, f32_bits(add_)), ar.flat("dx", "f32", B * C * P)
+    lib.check(lib.ccnet_cca_projection_adjoint_bf16(w.ptr, d.ptr, add.ptr, dx.ptr, B, C, P, K, w.ps, d.ps, d.bs, mem.stream), "adjoint")
+    ar.settle("projection_adjoint_bf16(d = 0)", (dx,))
+    r = {"dx": ar.get(dx)}
+    want = f32_bits(add_).reshape(r["dx"].shape)
+    assert np.array_equal(r["dx"], want), ("adjoint, d = 0", bcpk, form, np.argwhere(r["dx"] != want)[:4].tolist())
+    return r
+
+
 def check_adjoint(lib, r, bcpk):
     B, C, P, K = bcpk
     w_, d_ = _gemm_inputs(B + C + P + K, (1, C, K), (B, P, K))
@@ -550,6 +602,10 @@ def check_wgrad(lib, r, rncs):
     R, N, C, S = rncs
     d_, x_ = _gemm_inputs(R + N + C, (1, R, N), (1, R, C))
     d, x = bf16_vals(d_[0]).astype(np.float64), bf16_vals(x_[0]).astype(np.float64)
+    slab = (R + S * 64 - 1) // (S * 64) * 64                      # rows per slab as the entry point cuts them: a multiple of the k step
+    for sl in range(S):
+        if sl * slab >= R:                                        # a slab without rows: "every element written" means zeros
+            assert not r["part"].reshape(S, N, C)[sl].any(), ("wgrad: a slab without rows is not all +0", rncs, sl)
     got = r["part"].view(np.float32).reshape(S, N, C).astype(np.float64).sum(0)
     assert bool((np.abs(got - d.T @ x) <= 2e-6 * (np.abs(d).T @ np.abs(x)) + 1e-30).all())
 
@@ -609,10 +665,23 @@ for _shape in [(2, 8, 3, 5), (1, 200, 7, 9)]:
 for _C in (16, 64, 200):
     for _split in (True, False):
         _case(f"pack_projection-C{_C}-{'w3' if _split else 'no_w3'}", run_pack_projection, check_pack_projection, (_C, _split))
-for _mnk in [(37, 24, 72), (300, 136, 192)]:
+# The projection GEMMs (csrc/cca_gemm.hpp: tiles of 256 x 128, k steps of 64, three stages).  (M, N, K): the smallest problem
+# (nk = 1, a scalar N tail); one row past a tile (nk = 1, no tails); nk = 2 with a K tail and an odd N; nk = 4 -- the first nk
+# at which a stage it + 3 is filled -- with a K tail; nk = 9.  The loop's only, first and last k steps all run.
+for _mnk in [(37, 24, 72), (300, 136, 192), (1, 5, 8), (257, 128, 64), (255, 133, 72), (129, 72, 200), (513, 72, 520)]:
     _case(f"projection-{_sid(_mnk)}", run_projection, check_projection, (_mnk,))
-_case("adjoint-2x40x35x72", run_adjoint, check_adjoint, ((2, 40, 35, 72),))
-_case("wgrad-700x24x40x5", run_wgrad, check_wgrad, ((700, 24, 40, 5),))
+for _mnk in [(1, 8, 8), (257, 61, 64), (300, 136, 136), (130, 197, 200)]:
+    _case(f"projection_placement-{_sid(_mnk)}", run_projection_placement, check_in_run, (_mnk,))
+for _mnk in [(1, 5, 8), (300, 133, 72)]:
+    _case(f"projection_epilogue-{_sid(_mnk)}", run_projection_epilogue, check_in_run, (_mnk,))
+# (B, C, P, K): the second is one past a tile on either axis under either operand assignment, nk = 4 with a K tail
+for _bcpk in [(2, 40, 35, 72), (1, 72, 257, 64), (3, 264, 131, 200)]:
+    _case(f"adjoint-{_sid(_bcpk)}", run_adjoint, check_adjoint, (_bcpk,))
+_case("adjoint_zero-3x264x131x200", run_adjoint_zero, check_in_run, ((3, 264, 131, 200),))
+# (R, N, C, S): the smallest; one k step of one full tile; uneven slabs with N and C past a tile; slabs shorter than a k step;
+# more slabs than rows (slabs without rows write zeros)
+for _rncs in [(700, 24, 40, 5), (1, 8, 8, 1), (64, 128, 256, 1), (130, 136, 264, 3), (40, 8, 8, 5), (3, 8, 8, 5)]:
+    _case(f"wgrad-{_sid(_rncs)}", run_wgrad, check_wgrad, (_rncs,))
 
 _PLAIN = {}            # (back end, case id) -> the results on dense, unguarded buffers, computed once and left unchanged
 

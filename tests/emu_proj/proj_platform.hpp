@@ -18,8 +18,6 @@ __device__ inline u32x2v fbuf_load_x2(const cca::FBuf &b, int voff_bytes, int so
     return v;
 }
 
-__device__ inline void lds_wait_all(cca::u32x4 (&)[4], cca::u32x4 (&)[4]) {}
-
 }  // namespace proj
 
 #define PROJ_LAUNCH(kern, grid, block, stream, ...) emu::launch((grid), (block), [&]() { kern(__VA_ARGS__); })
