@@ -690,13 +690,46 @@ def ids(emulator):
     return [(cid, form) for cid, case in CASES.items() if not (emulator and case[4]) for form in FORMS]
 
 
+class _options:
+    """the case's library options set for the length of a ``with`` block, and restored"""
+
+    def __init__(self, lib, options):
+        self.lib, self.options = lib, options
+
+    def __enter__(self):
+        self.previous = {name: self.lib.set_option(name, value) for name, value in self.options.items()}
+
+    def __exit__(self, *exc):
+        for name, value in self.previous.items():
+            self.lib.set_option(name, value)
+        assert all(self.lib.get_option(name) == value for name, value in self.previous.items())
+
+
+def plain_case(lib, mem, cid, case=None):
+    """(``case``: a table entry that is not in CASES, under an id of its own)  the case on dense, unguarded buffers: computed once per back end -- by whichever test asks first, so a test that runs the
+    emulator in another mode (tests/test_emu_modes.py) asks BEFORE it sets the mode -- and left unchanged"""
+    run, check, args, options, _ = case or CASES[cid]
+    if (mem.name, cid) not in _PLAIN:
+        with _options(lib, options):
+            _PLAIN[mem.name, cid] = run(lib, mem, "dense", False, False, *args)
+    return _PLAIN[mem.name, cid]
+
+
+def run_case_bits(lib, mem, cid, form, case=None):
+    """one guarded run of the case in ``form``, held bitwise to ``plain_case``"""
+    run, check, args, options, _ = case or CASES[cid]
+    plain = plain_case(lib, mem, cid, case)
+    with _options(lib, options):
+        got = run(lib, mem, form, True, False, *args)
+    for name, ref in plain.items():
+        assert np.array_equal(got[name], ref), (cid, form, name, "differs from the dense, unguarded call", int((got[name] != ref).sum()))
+    return got
+
+
 def run_case(lib, mem, cid, form):
     run, check, args, options, _ = CASES[cid]
-    previous = {name: lib.set_option(name, value) for name, value in options.items()}
-    try:
-        if (mem.name, cid) not in _PLAIN:
-            _PLAIN[mem.name, cid] = run(lib, mem, "dense", False, False, *args)
-        plain = _PLAIN[mem.name, cid]
+    plain = plain_case(lib, mem, cid)
+    with _options(lib, options):
         got = run(lib, mem, form, True, False, *args)
         for name, ref in plain.items():
             assert np.array_equal(got[name], ref), (name, "differs from the dense, unguarded call", int((got[name] != ref).sum()))
@@ -705,7 +738,3 @@ def run_case(lib, mem, cid, form):
             assert np.array_equal(again[name], ref), (name, "depends on what the workspace / scratch held")
         if form == "padded":
             check(lib, got, *args)
-    finally:
-        for name, value in previous.items():
-            lib.set_option(name, value)
-    assert all(lib.get_option(name) == value for name, value in previous.items())

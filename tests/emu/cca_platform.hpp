@@ -65,7 +65,7 @@ __device__ inline void atomic_max_u32(unsigned *p, uint32_t v) { if (v > *p) *p 
 __device__ inline void mfma_f32_result_fence() {}
 __device__ inline void sched_fence() {}
 
-__device__ inline void wait_vmem_all() {}
+__device__ inline void wait_vmem_all() { emu::vmem_wait_all(); }
 __device__ inline int uniform(int v) { return v; }
 __device__ inline int recompute_here(int v) { return v; }
 
@@ -119,32 +119,46 @@ struct FBuf {
     uint32_t bytes;
 };
 __device__ inline FBuf make_fbuf(const float *p, size_t bytes) { return FBuf{(const char *)p, (uint32_t)bytes}; }
-__device__ inline float fbuf_load(const FBuf &b, int voff_bytes, int soff_bytes) {
+// Every primitive below that is one vector-memory instruction on the device reports itself to the emulator's vector-memory
+// queue (late mode) with the source line of its call: SITE is the defaulted pair (line, file) of the caller.
+#define CCA_EMU_SITE int site = __builtin_LINE(), const char *site_file = __builtin_FILE()
+__device__ inline float emu_fbuf_get(const FBuf &b, int voff_bytes, int soff_bytes) {
     const uint32_t o = (uint32_t)voff_bytes + (uint32_t)soff_bytes;
     if ((uint32_t)voff_bytes >= b.bytes || (size_t)o + 4 > b.bytes) return 0.f;
     float r;
     memcpy(&r, b.base + o, 4);
     return r;
 }
-__device__ inline f32x4 fbuf_load_x4(const FBuf &b, int voff_bytes, int soff_bytes) {
-    f32x4 v;
-    for (int e = 0; e < 4; ++e) v[e] = fbuf_load(b, voff_bytes + 4 * e, soff_bytes);
-    return v;
-}
-__device__ inline void fbuf_store(const FBuf &b, float v, int voff_bytes, int soff_bytes) {
+__device__ inline void emu_fbuf_put(const FBuf &b, float v, int voff_bytes, int soff_bytes) {
     const uint32_t o = (uint32_t)voff_bytes + (uint32_t)soff_bytes;
     if ((uint32_t)voff_bytes >= b.bytes || (size_t)o + 4 > b.bytes) return;      // out-of-range stores are dropped
     memcpy(const_cast<char *>(b.base) + o, &v, 4);
 }
-__device__ inline void fbuf_store_x4(const FBuf &b, f32x4 v, int voff_bytes, int soff_bytes) {
-    for (int e = 0; e < 4; ++e) fbuf_store(b, v[e], voff_bytes + 4 * e, soff_bytes);
+__device__ inline float fbuf_load(const FBuf &b, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    emu::vmem_note(site, site_file);
+    return emu_fbuf_get(b, voff_bytes, soff_bytes);
 }
-__device__ inline void fbuf_store_x2(const FBuf &b, uint32_t v0, uint32_t v1, int voff_bytes, int soff_bytes) {
+__device__ inline f32x4 fbuf_load_x4(const FBuf &b, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    emu::vmem_note(site, site_file);
+    f32x4 v;
+    for (int e = 0; e < 4; ++e) v[e] = emu_fbuf_get(b, voff_bytes + 4 * e, soff_bytes);
+    return v;
+}
+__device__ inline void fbuf_store(const FBuf &b, float v, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    emu::vmem_note(site, site_file);
+    emu_fbuf_put(b, v, voff_bytes, soff_bytes);
+}
+__device__ inline void fbuf_store_x4(const FBuf &b, f32x4 v, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    emu::vmem_note(site, site_file);
+    for (int e = 0; e < 4; ++e) emu_fbuf_put(b, v[e], voff_bytes + 4 * e, soff_bytes);
+}
+__device__ inline void fbuf_store_x2(const FBuf &b, uint32_t v0, uint32_t v1, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    emu::vmem_note(site, site_file);
     float f0, f1;
     memcpy(&f0, &v0, 4);
     memcpy(&f1, &v1, 4);
-    fbuf_store(b, f0, voff_bytes, soff_bytes);
-    fbuf_store(b, f1, voff_bytes + 4, soff_bytes);
+    emu_fbuf_put(b, f0, voff_bytes, soff_bytes);
+    emu_fbuf_put(b, f1, voff_bytes + 4, soff_bytes);
 }
 __device__ inline f32x4 lds_load_x4(const float *p) {
     f32x4 v;
@@ -153,18 +167,25 @@ __device__ inline f32x4 lds_load_x4(const float *p) {
 }
 __device__ inline void lds_store_x4(float *p, f32x4 v) { memcpy(p, &v, 16); }
 // LDS-DMA: every lane fetches one dword and the wave deposits the 64 dwords CONTIGUOUSLY at
-// lds_wave_base + lane (buffer_load_dword ... lds).  The emulator completes it synchronously.
-__device__ inline void fbuf_load_to_lds(const FBuf &b, float *lds_wave_base, int voff_bytes, int soff_bytes) {
-    lds_wave_base[emu::lane_id()] = fbuf_load(b, voff_bytes, soff_bytes);
+// lds_wave_base + lane (buffer_load_dword ... lds).  The source is read at issue; the data reaches LDS at once, or -- late
+// mode -- when a wait retires the instruction.
+__device__ inline void fbuf_load_to_lds(const FBuf &b, float *lds_wave_base, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    const float v = emu_fbuf_get(b, voff_bytes, soff_bytes);
+    emu::vmem_dma(site, site_file, lds_wave_base, emu::lane_id(), &v, 1, true);
 }
 // 16-byte form: every lane moves 4 consecutive dwords to lds_wave_base + 4 * lane
-__device__ inline void fbuf_load_to_lds_x4(const FBuf &b, float *lds_wave_base, int voff_bytes, int soff_bytes) {
-    for (int e = 0; e < 4; ++e)
-        lds_wave_base[4 * emu::lane_id() + e] = fbuf_load(b, voff_bytes + 4 * e, soff_bytes);
+__device__ inline void emu_dma_x4(const FBuf &b, float *lds_wave_base, int voff_bytes, int soff_bytes, bool visible, int site,
+                                  const char *site_file) {
+    float v[4];
+    for (int e = 0; e < 4; ++e) v[e] = emu_fbuf_get(b, voff_bytes + 4 * e, soff_bytes);
+    emu::vmem_dma(site, site_file, lds_wave_base, 4 * emu::lane_id(), v, 4, visible);
 }
-
-__device__ inline void fbuf_load_to_lds_x4_uncounted(const FBuf &b, float *lds_wave_base, int voff_bytes) {
-    fbuf_load_to_lds_x4(b, lds_wave_base, voff_bytes, 0);
+__device__ inline void fbuf_load_to_lds_x4(const FBuf &b, float *lds_wave_base, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    emu_dma_x4(b, lds_wave_base, voff_bytes, soff_bytes, true, site, site_file);
+}
+// the form the compiler does not see: a __syncthreads() does not wait for it
+__device__ inline void fbuf_load_to_lds_x4_uncounted(const FBuf &b, float *lds_wave_base, int voff_bytes, CCA_EMU_SITE) {
+    emu_dma_x4(b, lds_wave_base, voff_bytes, 0, false, site, site_file);
 }
 
 // ds_read_b64_tr_b16: see the product header.  Lane i of each 16-lane group receives, for j = 0..3, element (i & 3) of
@@ -190,9 +211,10 @@ __device__ inline u32x4 lds_read_x4_uncounted(const void *p) {
 template <int KEEP>
 __device__ inline void lds_wait_keep(u32x4 (&)[4], u32x4 (&)[4]) {}
 
-__device__ inline void barrier_lds_only() { __syncthreads(); }
+// the workgroup barriers differ in what they make the wave wait for (late mode); all of them synchronise the block
+__device__ inline void barrier_lds_only() { emu::block_barrier(emu::BAR_LDS_ONLY); }
 template <int KEEP>
-__device__ inline void barrier_dma_keep() { __syncthreads(); }
+__device__ inline void barrier_dma_keep(CCA_EMU_SITE) { emu::block_barrier(emu::BAR_KEEP, KEEP, site, site_file); }
 
 #define CCA_LDS_REGISTER(arr) do { emu::lds_register((void *)(arr), sizeof(arr)); __syncthreads(); } while (0)
 #define CCA_LDS_LD(p) (emu::lds_note_read((const void *)(p), __LINE__), *(p))
@@ -215,5 +237,10 @@ inline hipStream_t fork(hipStream_t) { return nullptr; }
 inline bool join(hipStream_t) { return true; }
 }  // namespace cca_side
 
-inline int cca_current_device_cus() { return 0; }      // the host default (256) applies
-inline int cca_current_device() { return 0; }
+// The emulator's "current device".  Device 0 reports no CU count: the host default (256) applies, and with it the plans of a
+// big device, which cut a small problem's strips into one channel range per workgroup.  A test may switch to another device
+// id with a CU count of its choice (cca_emu_set_device, tests/emu/cca_emu_tu.cpp; the host caches the count per id): on two CUs
+// a small problem runs whole rounds of strips, every workgroup walking ALL its channel groups -- the multi-stage paths.
+inline int *cca_emu_device() { static int dev_cus[2] = {0, 0}; return dev_cus; }
+inline int cca_current_device_cus() { return cca_emu_device()[1]; }
+inline int cca_current_device() { return cca_emu_device()[0]; }

@@ -2,14 +2,17 @@
 #include "hip_emu.hpp"
 
 #include <algorithm>
+#include <deque>
 #include <limits>
 #include <map>
+#include <string>
 #include <vector>
 
 namespace emu {
 
 dim3 g_block, g_bdim, g_gdim;
 Lane *g_cur = nullptr;
+bool g_late = false;
 
 namespace {
 
@@ -21,6 +24,16 @@ struct Access {
     bool write;
 };
 
+// one lane's share of a vector-memory instruction, as the lane issued it (late mode)
+struct VEvent {
+    const char *file;
+    int line;
+    float *dst;                      // LDS-DMA: the wave-uniform destination; nullptr: a load or a store
+    int off, ndw;
+    float data[4];
+    bool visible;
+};
+
 struct Fiber {
     Lane lane;
     void *sp = nullptr;
@@ -30,6 +43,28 @@ struct Fiber {
     int xparity = 0;                 // alternates the exchange buffer (one rendez-vous per collective)
     std::vector<Access> acc;
     std::map<int, int> occ;
+    std::vector<VEvent> vlog;        // vector-memory instructions issued since the wave's last rendez-vous
+    int bar_kind = BAR_SYNC, bar_keep = 0, bar_line = 0;
+    const char *bar_file = nullptr;
+    int site_line = 0;
+    const char *site_file = nullptr;
+    bool wait_all = false;
+};
+
+// one wave instruction in flight
+struct LaneWrite { float *dst; int ndw; float data[4]; };
+struct VEntry {
+    const char *file;
+    int line;
+    bool dma, visible;
+    bool unordered;                  // not one instruction: what the lanes of a wave issued in no order the source determines
+    int lane_a, lane_b;              // ... the two lanes that disagreed (file / line: what lane_a issued and lane_b did not)
+    std::vector<LaneWrite> writes;
+};
+struct SiteStat { unsigned long long runs = 0, unlanded = 0; int max_keep = -1, max_keep_unlanded = -1; };
+struct VStats {
+    unsigned long long dma_issued = 0, retired_counted = 0;
+    std::map<std::string, SiteStat> sites;
 };
 
 constexpr size_t kStack = 256 * 1024;
@@ -43,6 +78,10 @@ Stats g_stats = {};
 void *lds_base = nullptr;
 size_t lds_bytes = 0;
 bool lds_trace = false;
+bool reversed = false;
+int keep_plus = 0;
+std::vector<std::deque<VEntry>> vqueue;      // [wave]
+VStats g_vstats;
 
 extern "C" void emu_switch(void **save_sp, void *load_sp);
 asm(R"(
@@ -89,6 +128,130 @@ void prepare(Fiber &f) {
     f.xparity = 0;
     f.acc.clear();
     f.occ.clear();
+    f.vlog.clear();
+    f.site_line = 0;
+    f.site_file = nullptr;
+    f.wait_all = false;
+}
+
+std::string site_name(const char *file, int line) {
+    const char *base = file ? std::strrchr(file, '/') : nullptr;
+    return std::string(base ? base + 1 : (file ? file : "?")) + ":" + std::to_string(line);
+}
+
+bool same_instr(const VEvent &a, const VEvent &b) { return a.line == b.line && a.file == b.file && a.dst == b.dst; }
+
+// Lanes are separate fibers: the instructions they issued since the wave's last rendez-vous are grouped into wave instructions
+// here.  The order is the longest lane's; every other lane's sequence must be a subsequence of it (instruction = source line +,
+// for a DMA, the wave-uniform LDS destination).  A wave whose lanes disagree -- two lanes that each issued something the other
+// did not, the two sides of a divergent branch -- has no order, and no count, that the source determines.  What it issued is
+// queued as ONE unordered entry: harmless where a wait retires it whole (the stores of an epilogue), fatal where a counted
+// barrier would have to count it (retire_at_barrier) -- the emulator stops rather than guess.
+void merge_wave(int w, int nthreads) {
+    int lo = w * 64, hi = std::min(nthreads, lo + 64), longest = -1;
+    for (int t = lo; t < hi; ++t)
+        if (!fibers[t].vlog.empty() && (longest < 0 || fibers[t].vlog.size() > fibers[longest].vlog.size())) longest = t;
+    if (longest < 0) return;
+    const std::vector<VEvent> ref = fibers[longest].vlog;
+    std::vector<VEntry> merged(ref.size());
+    for (size_t i = 0; i < ref.size(); ++i)
+        merged[i] = VEntry{ref[i].file, ref[i].line, ref[i].dst != nullptr, ref[i].visible, false, 0, 0, {}};
+    VEntry group{nullptr, 0, false, false, false, 0, 0, {}};
+    for (int t = lo; t < hi && !group.unordered; ++t) {
+        size_t at = 0;
+        for (const VEvent &e : fibers[t].vlog) {
+            while (at < ref.size() && !same_instr(ref[at], e)) ++at;
+            if (at == ref.size()) {
+                group = VEntry{e.file, e.line, false, false, true, t - lo, longest - lo, {}};
+                break;
+            }
+            if (e.dst) {
+                LaneWrite lw{e.dst + e.off, e.ndw, {e.data[0], e.data[1], e.data[2], e.data[3]}};
+                merged[at].writes.push_back(lw);
+            }
+            ++at;
+        }
+    }
+    if (group.unordered) {
+        merged.clear();
+        for (int t = lo; t < hi; ++t)
+            for (const VEvent &e : fibers[t].vlog)
+                if (e.dst) {
+                    LaneWrite lw{e.dst + e.off, e.ndw, {e.data[0], e.data[1], e.data[2], e.data[3]}};
+                    group.writes.push_back(lw);
+                    group.dma = true;
+                    group.visible |= e.visible;
+                }
+        merged.push_back(group);
+    }
+    for (int t = lo; t < hi; ++t) fibers[t].vlog.clear();
+    for (VEntry &m : merged) {
+        if (m.dma && !m.unordered) g_vstats.dma_issued++;
+        vqueue[w].push_back(std::move(m));
+    }
+}
+
+void retire_oldest(int w) {
+    VEntry &e = vqueue[w].front();
+    for (const LaneWrite &lw : e.writes) std::memcpy(lw.dst, lw.data, size_t(lw.ndw) * 4);
+    vqueue[w].pop_front();
+}
+
+[[noreturn]] void cannot_count(int w, const VEntry &e, const char *what, const char *file, int line) {
+    std::fprintf(stderr, "emu: block (%u,%u,%u) wave %d: %s %s has to count vector-memory instructions that have no single order: "
+                 "lane %d issued %s where lane %d, with the longest sequence, did not\n", g_block.x, g_block.y, g_block.z, w, what,
+                 site_name(file, line).c_str(), e.lane_a, site_name(e.file, e.line).c_str(), e.lane_b);
+    std::abort();
+}
+
+int unlanded(int w) {
+    int n = 0;
+    for (const VEntry &e : vqueue[w]) n += e.dma;
+    return n;
+}
+
+// the block barrier is about to be released: every wave waits for what its barrier makes it wait for
+void retire_at_barrier(int w, int nthreads) {
+    int lo = w * 64, hi = std::min(nthreads, lo + 64);
+    const Fiber *first = nullptr;
+    for (int t = lo; t < hi; ++t) {
+        const Fiber &f = fibers[t];
+        if (f.state != WAIT_BLOCK) continue;
+        if (!first) first = &f;
+        else if (f.bar_kind != first->bar_kind || f.bar_keep != first->bar_keep || f.bar_line != first->bar_line) {
+            std::fprintf(stderr, "emu: block (%u,%u,%u) wave %d: lanes %d and %d meet in different barriers (%s keep %d, %s keep %d)\n",
+                         g_block.x, g_block.y, g_block.z, w, first->index - lo, t - lo,
+                         site_name(first->bar_file, first->bar_line).c_str(), first->bar_keep,
+                         site_name(f.bar_file, f.bar_line).c_str(), f.bar_keep);
+            std::abort();
+        }
+    }
+    if (!first) return;
+    std::deque<VEntry> &q = vqueue[w];
+    if (first->bar_kind == BAR_SYNC) {
+        int youngest = -1;
+        for (size_t i = 0; i < q.size(); ++i)
+            if (q[i].dma && q[i].visible) youngest = int(i);
+        // (an unordered entry that holds a visible fill and is the last to go: what else of it the barrier waits for is unknown)
+        if (youngest >= 0 && q[youngest].unordered) cannot_count(w, q[youngest], "__syncthreads() at", first->bar_file, first->bar_line);
+        for (int i = 0; i <= youngest; ++i) retire_oldest(w);
+    } else if (first->bar_kind == BAR_KEEP) {
+        SiteStat &st = g_vstats.sites[site_name(first->bar_file, first->bar_line)];
+        const int keep = std::max(0, first->bar_keep), pending = unlanded(w);
+        st.runs++;
+        st.max_keep = std::max(st.max_keep, keep);
+        if (pending) {
+            st.unlanded++;
+            st.max_keep_unlanded = std::max(st.max_keep_unlanded, keep);
+        }
+        for (int i = 0; i < keep + keep_plus && i < int(q.size()); ++i)            // the entries the count is counted in
+            if (q[q.size() - 1 - i].unordered)
+                cannot_count(w, q[q.size() - 1 - i], "the counted barrier at", first->bar_file, first->bar_line);
+        while (int(q.size()) > keep + keep_plus) {
+            if (q.front().dma) g_vstats.retired_counted++;
+            retire_oldest(w);
+        }
+    }
 }
 
 void analyse_lds(int nthreads) {
@@ -124,10 +287,11 @@ void run_block(int nthreads) {
     xbuf.assign(size_t(nwaves) * 2 * 64, 0);
     xwide.assign(size_t(nwaves) * 2 * 64 * 32, 0);
     for (int t = 0; t < nthreads; ++t) prepare(fibers[t]);
+    vqueue.assign(nwaves, {});
     for (;;) {
         bool progressed = false, all_done = true;
-        for (int t = 0; t < nthreads; ++t) {
-            Fiber &f = fibers[t];
+        for (int i = 0; i < nthreads; ++i) {
+            Fiber &f = fibers[reversed ? nthreads - 1 - i : i];
             if (f.state == DONE) continue;
             all_done = false;
             if (f.state != RUNNABLE) continue;
@@ -145,8 +309,17 @@ void run_block(int nthreads) {
                 if (fibers[t].state == WAIT_WAVE) ++waiting;
             }
             if (alive && waiting == alive) {
+                bool wait_all = false;
                 for (int t = lo; t < hi; ++t)
-                    if (fibers[t].state == WAIT_WAVE) fibers[t].state = RUNNABLE;
+                    if (fibers[t].state == WAIT_WAVE) {
+                        fibers[t].state = RUNNABLE;
+                        wait_all |= fibers[t].wait_all;
+                        fibers[t].wait_all = false;
+                    }
+                if (g_late) {
+                    merge_wave(w, nthreads);
+                    while (wait_all && !vqueue[w].empty()) retire_oldest(w);
+                }
                 progressed = true;
             }
         }
@@ -157,7 +330,13 @@ void run_block(int nthreads) {
             if (fibers[t].state == WAIT_BLOCK) ++waiting;
         }
         if (alive && waiting == alive) {
-            for (int t = 0; t < nthreads; ++t) fibers[t].state = RUNNABLE;
+            if (g_late)
+                for (int w = 0; w < nwaves; ++w) {
+                    merge_wave(w, nthreads);
+                    retire_at_barrier(w, nthreads);
+                }
+            for (int t = 0; t < nthreads; ++t)
+                if (fibers[t].state == WAIT_BLOCK) fibers[t].state = RUNNABLE;
             progressed = true;
         }
         if (!progressed) {
@@ -166,6 +345,11 @@ void run_block(int nthreads) {
             std::abort();
         }
     }
+    if (g_late)                                            // the end of the kernel: everything lands
+        for (int w = 0; w < nwaves; ++w) {
+            merge_wave(w, nthreads);
+            while (!vqueue[w].empty()) retire_oldest(w);
+        }
     analyse_lds(nthreads);
 }
 
@@ -174,6 +358,10 @@ void run_block(int nthreads) {
 void launch(dim3 grid, dim3 block, const std::function<void()> &body) {
     const char *env = std::getenv("CCA_EMU_LDS");
     lds_trace = env && env[0] == '1';
+    auto on = [](const char *name) { const char *v = std::getenv(name); return v && v[0] == '1'; };
+    g_late = on("CCA_EMU_LATE_DMA");
+    reversed = on("CCA_EMU_REVERSE");
+    keep_plus = on("CCA_EMU_KEEP_PLUS") ? 1 : 0;
     g_gdim = grid;
     g_bdim = block;
     int nthreads = int(block.x * block.y * block.z);
@@ -195,8 +383,41 @@ void launch(dim3 grid, dim3 block, const std::function<void()> &body) {
     cur_body = nullptr;
 }
 
-void block_barrier() {
-    cur_fiber->state = WAIT_BLOCK;
+void block_barrier(int kind, int keep, int line, const char *file) {
+    Fiber &f = *cur_fiber;
+    f.bar_kind = kind;
+    f.bar_keep = keep;
+    f.bar_line = f.site_file ? f.site_line : line;
+    f.bar_file = f.site_file ? f.site_file : file;
+    f.site_file = nullptr;
+    f.state = WAIT_BLOCK;
+    yield_to_scheduler();
+}
+
+void set_barrier_site(int line, const char *file) {
+    cur_fiber->site_line = line;
+    cur_fiber->site_file = file;
+}
+
+void vmem_note(int line, const char *file) {
+    if (g_late) cur_fiber->vlog.push_back(VEvent{file, line, nullptr, 0, 0, {0, 0, 0, 0}, false});
+}
+
+void vmem_dma(int line, const char *file, float *dst_wave_base, int lane_dword_off, const float *data, int ndw, bool compiler_visible) {
+    if (!g_late) {
+        std::memcpy(dst_wave_base + lane_dword_off, data, size_t(ndw) * 4);
+        return;
+    }
+    VEvent e{file, line, dst_wave_base, lane_dword_off, ndw, {0, 0, 0, 0}, compiler_visible};
+    std::memcpy(e.data, data, size_t(ndw) * 4);
+    cur_fiber->vlog.push_back(e);
+}
+
+void vmem_wait_all() {
+    if (!g_late) return;
+    Fiber &f = *cur_fiber;
+    f.wait_all = true;
+    f.state = WAIT_WAVE;
     yield_to_scheduler();
 }
 
@@ -252,6 +473,7 @@ void lds_note_read(const void *addr, int site) { note(addr, site, false); }
 void lds_note_write(const void *addr, int site) { note(addr, site, true); }
 
 Stats &stats() { return g_stats; }
+static VStats &vmem_stats() { return g_vstats; }
 
 }  // namespace emu
 
@@ -262,3 +484,21 @@ extern "C" void cca_emu_stats(unsigned long long *out6) {
     out6[3] = s.lds_write_cycles; out6[4] = s.mfma; out6[5] = s.launches;
 }
 extern "C" void cca_emu_reset_stats() { emu::stats() = emu::Stats{}; }
+
+// the vector-memory model's counters (late mode), as text: "dma_issued N", "retired_by_counted_barriers N", then per source line
+// of a counted barrier "site FILE:LINE RUNS RUNS_WITH_AN_UNLANDED_DMA MAX_KEEP MAX_KEEP_WITH_AN_UNLANDED_DMA" (-1: never).
+// Returns the length of the whole text; writes at most cap - 1 characters of it and a terminator.
+extern "C" size_t emu_vmem_stats(char *out, size_t cap) {
+    const emu::VStats &v = emu::vmem_stats();
+    std::string s = "dma_issued " + std::to_string(v.dma_issued) + "\nretired_by_counted_barriers " + std::to_string(v.retired_counted) + "\n";
+    for (const auto &kv : v.sites)
+        s += "site " + kv.first + " " + std::to_string(kv.second.runs) + " " + std::to_string(kv.second.unlanded) + " " +
+             std::to_string(kv.second.max_keep) + " " + std::to_string(kv.second.max_keep_unlanded) + "\n";
+    if (out && cap) {
+        const size_t n = std::min(cap - 1, s.size());
+        std::memcpy(out, s.data(), n);
+        out[n] = 0;
+    }
+    return s.size();
+}
+extern "C" void emu_vmem_reset_stats() { emu::vmem_stats() = emu::VStats{}; }

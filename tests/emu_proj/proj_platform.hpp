@@ -7,10 +7,11 @@ namespace proj {
 
 typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
 
-__device__ inline u32x2v fbuf_load_x2(const cca::FBuf &b, int voff_bytes, int soff_bytes) {
+__device__ inline u32x2v fbuf_load_x2(const cca::FBuf &b, int voff_bytes, int soff_bytes, CCA_EMU_SITE) {
+    emu::vmem_note(site, site_file);                 // one vector-memory instruction
     u32x2v v;
     for (int e = 0; e < 2; ++e) {
-        const float f = cca::fbuf_load(b, voff_bytes + 4 * e, soff_bytes);
+        const float f = cca::emu_fbuf_get(b, voff_bytes + 4 * e, soff_bytes);
         uint32_t u;
         memcpy(&u, &f, 4);
         v[e] = u;

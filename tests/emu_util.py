@@ -19,7 +19,7 @@ HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
 
 
 def _sources():
-    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp", "cca_platform.hpp")]
+    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp", "cca_platform.hpp", "cca_emu_tu.cpp")]
     srcs += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
     srcs.append(os.path.join(ROOT, "include", "ccnet_cca.h"))
     return srcs
@@ -32,7 +32,7 @@ def build_emu(force=False):
             return EMU_LIB
     cmd = [cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
            "-I" + EMU_DIR, "-I" + CSRC,          # tests/emu FIRST: <cca_platform.hpp> resolves to the emulator's
-           os.path.join(CSRC, "cca_api.hip"),
+           os.path.join(EMU_DIR, "cca_emu_tu.cpp"),   # cca_api.hip, with counted barriers charged to their callers' lines
            os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB]
     subprocess.run(cmd, check=True, cwd=ROOT)
     return EMU_LIB

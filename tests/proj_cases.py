@@ -85,11 +85,18 @@ def launch_gemm(lib, mem, form, a_, w_, bias_, add_, what="gemm_bf16"):
     return ar.get(out)[0]
 
 
+def gemm_bits(lib, mem, cid, variant):
+    """the guarded call of one case -> the result's bf16 bit patterns"""
+    use_bias, use_add, form = GEMM_VARIANTS[variant]
+    a, w, add, bias, ref = gemm_inputs(_mnk(cid))
+    return launch_gemm(lib, mem, form, a, w, bias if use_bias else None, add if use_add else None)
+
+
 def run_gemm(lib, mem, cid, variant):
     mnk = _mnk(cid)
     use_bias, use_add, form = GEMM_VARIANTS[variant]
     a, w, add, bias, ref = gemm_inputs(mnk)
-    got = bf16_vals(launch_gemm(lib, mem, form, a, w, bias if use_bias else None, add if use_add else None)).astype(np.float64)
+    got = bf16_vals(gemm_bits(lib, mem, cid, variant)).astype(np.float64)
     want, mag = ref["prod"], ref["mag"]
     if use_bias:
         want, mag = want + bias.astype(np.float64), mag + np.abs(bias.astype(np.float64))
