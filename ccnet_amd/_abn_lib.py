@@ -1,15 +1,16 @@
 """ctypes binding of the C ABI declared in include/ccnet_abn.h (activated batch normalisation on the device).
 
 The product loads ``ccnet_amd/csrc_abn/libccnet_abn.so`` (built for gfx950 by ``__graft_entry__.build()``), a library of its
-own beside the other four.  As with :mod:`ccnet_amd._lib` there is no fallback: a missing library raises.
+own beside the other five (one scaffold, six libraries; :mod:`ccnet_amd._clib` holds what the bindings share).
+As with :mod:`ccnet_amd._lib` there is no fallback: a missing library raises.
 """
 from __future__ import annotations
 
-import ctypes
 import os
-import re
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_size_t, c_void_p
 from typing import List, Optional
+
+from . import _clib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc_abn")
@@ -51,9 +52,7 @@ ACTIVATIONS = {"identity": CCNET_ABN_IDENTITY, "none": CCNET_ABN_IDENTITY, "relu
 
 def declared_symbols(header: str = HEADER_PATH) -> List[str]:
     """Every function name include/ccnet_abn.h declares."""
-    with open(header) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ccnet_\w+)\s*\(", text)))
+    return _clib.declared_symbols(header)
 
 
 def make_desc(dtype: int, N: int, C: int, H: int, W: int, activation: int, act_param: float, gamma_mode: int,
@@ -65,31 +64,11 @@ class AbnError(RuntimeError):
     pass
 
 
-class AbnLibrary:
+class AbnLibrary(_clib.CLibrary):
     """A loaded libccnet_abn.so (or, in the CPU tests, the emulator build of the same sources)."""
 
-    def __init__(self, path: str = LIB_PATH):
-        if not os.path.exists(path):
-            raise AbnError(
-                f"{path} not found: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()').  "
-                "ccnet_amd has no CPU or PyTorch fallback for the ABN kernels.")
-        self.path = path
-        self.dll = ctypes.CDLL(path)
-        for name, (res, args) in _PROTOTYPES.items():
-            fn = getattr(self.dll, name)
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name, fn)
-        if self.ccnet_abn_version() != CCNET_ABN_VERSION:
-            raise AbnError(f"{path} exports C ABI version {self.ccnet_abn_version()}, this binding is written against "
-                           f"{CCNET_ABN_VERSION} (include/ccnet_abn.h): rebuild the extension")
-
-    def last_error(self) -> str:
-        return self.ccnet_abn_last_error_string().decode()
-
-    def check(self, code: int, what: str = "") -> None:
-        if code != 0:
-            raise AbnError(f"{what or 'ccnet_abn'} failed with code {code}: {self.last_error()}")
+    PREFIX, ERROR = "ccnet_abn", AbnError
+    KERNELS = "ABN kernels"
 
 
 _lib: Optional[AbnLibrary] = None
@@ -97,8 +76,4 @@ _lib: Optional[AbnLibrary] = None
 
 def get_lib() -> AbnLibrary:
     """The process-wide device library; raises AbnError when it has not been built."""
-    global _lib
-    if _lib is None:
-        import torch  # noqa: F401  (map PyTorch's HIP runtime first, as _lib.get_lib does)
-        _lib = AbnLibrary(LIB_PATH)
-    return _lib
+    return AbnLibrary.shared()

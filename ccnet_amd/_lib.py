@@ -2,16 +2,17 @@
 
 The product loads ``ccnet_amd/csrc/libccnet_cca.so`` (built for gfx950 by ``__graft_entry__.build()``).
 There is deliberately NO fallback: if the library is missing, or a tensor is not on a HIP device, the
-callers in :mod:`ccnet_amd.functions` raise.  ``import torch`` must precede the ``CDLL`` so that the HIP
-runtime already mapped by PyTorch (same SONAME ``libamdhip64.so.7``) is the one the library binds to.
+callers in :mod:`ccnet_amd.functions` raise.  Loading, the prototypes, the version check and the errors are the part shared
+with the other five bindings, :mod:`ccnet_amd._clib`, which also imports torch before the ``CDLL``.
 """
 from __future__ import annotations
 
 import ctypes
 import os
-import re
 from ctypes import c_char_p, c_int, c_long, c_size_t, c_void_p
 from typing import List, Optional
+
+from . import _clib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libccnet_cca.so")
@@ -83,33 +84,19 @@ _PROTOTYPES = {
 
 def declared_symbols(header: str = HEADER_PATH) -> List[str]:
     """Every function name include/ccnet_cca.h declares (used by the symbol-export test)."""
-    with open(header) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ccnet_\w+)\s*\(", text)))
+    return _clib.declared_symbols(header)
 
 
 class CcaError(RuntimeError):
     pass
 
 
-class CcaLibrary:
+class CcaLibrary(_clib.CLibrary):
     """A loaded libccnet_cca.so (or, in the CPU tests, the emulator build of the same sources)."""
 
-    def __init__(self, path: str = LIB_PATH):
-        if not os.path.exists(path):
-            raise CcaError(
-                f"{path} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()').  "
-                "ccnet_amd has no CPU or PyTorch fallback for the criss-cross attention kernels.")
-        self.path = path
-        self.dll = ctypes.CDLL(path)
-        for name, (res, args) in _PROTOTYPES.items():
-            fn = getattr(self.dll, name)      # AttributeError if the symbol is not exported
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name, fn)
-        if self.ccnet_cca_version() != CCNET_CCA_VERSION:
-            raise CcaError(f"{path} exports C ABI version {self.ccnet_cca_version()}, this binding is written against "
-                           f"{CCNET_CCA_VERSION} (include/ccnet_cca.h): rebuild the extension")
+    PREFIX, ERROR = "ccnet_cca", CcaError
+    KERNELS = "criss-cross attention kernels"
+    BUILD_FIRST = "build the HIP extension first"
 
     # ---- options by name: the C calls return a status and pass values through out-parameters ----
     def set_option(self, name, value: int) -> int:
@@ -155,13 +142,6 @@ class CcaLibrary:
     def ccnet_cca_planes_workspace_bytes(self, B, C, Cq, H, W, backward) -> int:
         return self.ccnet_cca_workspace_bytes(CCNET_WS_PLANES_BACKWARD if backward else CCNET_WS_PLANES_FORWARD, B, C, Cq, H, W)
 
-    def last_error(self) -> str:
-        return self.ccnet_cca_last_error_string().decode()
-
-    def check(self, code: int, what: str = "") -> None:
-        if code != 0:
-            raise CcaError(f"{what or 'ccnet_cca'} failed with code {code}: {self.last_error()}")
-
     def profile_launches(self, fn, cap: int = 256):
         """Run ``fn()`` with the launch profiler armed: [(kernel name, ms)] of every launch the library issued, in
         issue order (HIP-event pairs on the launch stream; a measurement aid, see ccnet_cca_profile_begin)."""
@@ -186,11 +166,7 @@ _lib: Optional[CcaLibrary] = None
 
 def get_lib() -> CcaLibrary:
     """The process-wide device library; raises CcaError when it has not been built."""
-    global _lib
-    if _lib is None:
-        import torch  # noqa: F401  (map PyTorch's HIP runtime first, see module docstring)
-        _lib = CcaLibrary(LIB_PATH)
-    return _lib
+    return CcaLibrary.shared()
 
 
 def kernel_source_sha16() -> str:

@@ -1,15 +1,16 @@
 """ctypes binding of the C ABI declared in include/ccnet_proj.h (the module's bf16 projections on the library's own MFMA GEMM).
 
 The product loads ``ccnet_amd/csrc_proj/libccnet_proj.so`` (built for gfx950 by ``__graft_entry__.build()``), a library of its
-own beside the other five.  As with :mod:`ccnet_amd._lib` there is no fallback: a missing library raises.
+own beside the other five (one scaffold, six libraries; :mod:`ccnet_amd._clib` holds what the bindings share).
+As with :mod:`ccnet_amd._lib` there is no fallback: a missing library raises.
 """
 from __future__ import annotations
 
-import ctypes
 import os
-import re
 from ctypes import c_char_p, c_int, c_long, c_size_t, c_void_p
 from typing import List, Optional, Tuple
+
+from . import _clib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc_proj")
@@ -38,9 +39,7 @@ _PROTOTYPES = {
 
 def declared_symbols(header: str = HEADER_PATH) -> List[str]:
     """Every function name include/ccnet_proj.h declares."""
-    with open(header) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ccnet_\w+)\s*\(", text)))
+    return _clib.declared_symbols(header)
 
 
 def gemm_contract_ok(N: int, K: int, lda: int, ldw: int, ldo: int, ldadd: Optional[int] = None) -> bool:
@@ -67,31 +66,12 @@ class ProjError(RuntimeError):
     pass
 
 
-class ProjLibrary:
+class ProjLibrary(_clib.CLibrary):
     """A loaded libccnet_proj.so (or, in the CPU tests, the emulator build of the same sources)."""
 
-    def __init__(self, path: str = LIB_PATH):
-        if not os.path.exists(path):
-            raise ProjError(
-                f"{path} not found: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()').  "
-                "ccnet_amd has no CPU or PyTorch fallback for the projection kernels.")
-        self.path = path
-        self.dll = ctypes.CDLL(path)
-        for name, (res, args) in _PROTOTYPES.items():
-            fn = getattr(self.dll, name)
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name, fn)
-        if self.ccnet_proj_version() != CCNET_PROJ_VERSION:
-            raise ProjError(f"{path} exports C ABI version {self.ccnet_proj_version()}, this binding is written against "
-                            f"{CCNET_PROJ_VERSION} (include/ccnet_proj.h): rebuild the extension")
-
-    def last_error(self) -> str:
-        return self.ccnet_proj_last_error().decode()
-
-    def check(self, code: int, what: str = "") -> None:
-        if code != 0:
-            raise ProjError(f"{what or 'ccnet_proj'} failed with code {code}: {self.last_error()}")
+    PREFIX, ERROR = "ccnet_proj", ProjError
+    KERNELS = "projection kernels"
+    LAST_ERROR = "ccnet_proj_last_error"
 
 
 _lib: Optional[ProjLibrary] = None
@@ -99,8 +79,4 @@ _lib: Optional[ProjLibrary] = None
 
 def get_lib() -> ProjLibrary:
     """The process-wide device library; raises ProjError when it has not been built."""
-    global _lib
-    if _lib is None:
-        import torch  # noqa: F401  (map PyTorch's HIP runtime first, as _lib.get_lib does)
-        _lib = ProjLibrary(LIB_PATH)
-    return _lib
+    return ProjLibrary.shared()

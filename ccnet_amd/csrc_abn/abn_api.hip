@@ -3,24 +3,14 @@
 #include "ccnet_abn.h"
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "abn_kernels.hpp"
 
+#define CCNET_ERROR_PREFIX "ccnet_abn: "
+#include "../csrc_common/ccnet_host.hpp"
+
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    int n = snprintf(g_err, sizeof g_err, "ccnet_abn: ");
-    vsnprintf(g_err + n, sizeof g_err - n, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 struct Grid {
     int HW, S, cpp;
@@ -82,12 +72,6 @@ int check_source(const ccnet_abn_desc *d, int source, const char *what) {
     if (source == CCNET_ABN_FROM_OUTPUT &&
         (d->activation == CCNET_ABN_RELU || (d->activation == CCNET_ABN_LEAKY_RELU && !(d->act_param > 0.f))))
         return fail(-1, "%s: the input cannot be rebuilt from the output of relu or leaky_relu with slope 0", what);
-    return 0;
-}
-
-int launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, "%s launch failed: %s", what, hipGetErrorString(e));
     return 0;
 }
 

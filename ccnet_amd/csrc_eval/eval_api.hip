@@ -2,23 +2,12 @@
 // The launch goes on the caller's stream; the tile origins travel as a kernel argument and nothing waits for the device.
 #include "ccnet_eval.h"
 
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "eval_kernels.hpp"
 
+#define CCNET_ERROR_PREFIX "ccnet_eval: "
+#include "../csrc_common/ccnet_host.hpp"
+
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    int n = snprintf(g_err, sizeof g_err, "ccnet_eval: ");
-    vsnprintf(g_err + n, sizeof g_err - n, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 // PyTorch's area_pixel_compute_scale for align_corners=True, in fp32
 float align_corners_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
@@ -61,9 +50,7 @@ __attribute__((visibility("default"))) int ccnet_eval_sliding_f32(const float *t
     const dim3 grid((unsigned)((H * W + segeval::kPixPerBlock - 1) / segeval::kPixPerBlock), (unsigned)N);
     EVAL_LAUNCH(segeval::sliding_kernel, grid, dim3(segeval::kThreads), lds, static_cast<hipStream_t>(stream), tile_logits, g, G,
                 labels, ignore_label, probs_out, pred_out, confusion);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, "sliding launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launched("sliding");
 }
 
 }  // extern "C"

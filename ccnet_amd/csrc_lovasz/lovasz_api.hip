@@ -2,25 +2,12 @@
 // Every launch goes on the caller's stream and nothing waits for the device.
 #include "ccnet_lovasz.h"
 
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "lovasz_kernels.hpp"
 
+#define CCNET_ERROR_PREFIX "ccnet_lovasz: "
+#include "../csrc_common/ccnet_host.hpp"
+
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    int n = snprintf(g_err, sizeof g_err, "ccnet_lovasz: ");
-    vsnprintf(g_err + n, sizeof g_err - n, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
 struct Layout {
     int HW, L, S, nt;
@@ -56,15 +43,6 @@ bool layout(int B, int C, int H, int W, int per_image, Layout &L) {
     L.seg_den = o;    o += align256(4 * (size_t)L.S);
     L.total = o;
     return true;
-}
-
-template <class T>
-T *at(void *ws, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(ws) + off); }
-
-int launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, "%s launch failed: %s", what, hipGetErrorString(e));
-    return 0;
 }
 
 }  // namespace

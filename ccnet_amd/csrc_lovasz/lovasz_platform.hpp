@@ -1,16 +1,16 @@
-// lovasz_platform.hpp -- gfx950 implementations of the few device primitives the Lovász kernels use (wave64 ballot and
-// lane rank, the butterfly sum, the LDS histogram increment, the launch macro).  The CPU test-suite has a header of the same
-// name under tests/emu_lovasz/ that implements them in the SIMT emulator; the product never sees it.
+// lovasz_platform.hpp -- gfx950 implementations of the few device primitives the Lovász kernels use.  Its own: the wave64
+// ballot and lane rank.  From csrc_common/ccnet_device.hpp: the butterfly sum, the LDS histogram increment, the launch macro.
+// The CPU test-suite has a header of the same name under tests/emu_lovasz/ that implements them in the SIMT emulator; the
+// product never sees it.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
+#include "../csrc_common/ccnet_device.hpp"
 
 namespace lovasz {
 
-constexpr int kWave = 64;
-
-__device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
+using ccnet_common::kWave;
+using ccnet_common::lane_id;
+using ccnet_common::lds_inc;
+using ccnet_common::wave_sum;
 
 // 64-bit mask of the lanes of this wave whose `pred` is set (every lane of the wave must call it)
 __device__ __forceinline__ uint64_t ballot(bool pred) { return (uint64_t)__ballot(pred); }
@@ -22,16 +22,6 @@ __device__ __forceinline__ unsigned rank_below(uint64_t mask) {
 
 __device__ __forceinline__ unsigned popc64(uint64_t m) { return (unsigned)__popcll(m); }
 
-// butterfly sum over the 64 lanes: every lane gets the same, order-fixed result
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = kWave / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-
-// integer increment of an LDS counter (ds_add_u32): counts are order-independent, so the histogram stays deterministic
-__device__ __forceinline__ void lds_inc(unsigned *p) { atomicAdd(p, 1u); }
-
 }  // namespace lovasz
 
-#define LOVASZ_LAUNCH(kern, grid, block, stream, ...) kern<<<(grid), (block), 0, (stream)>>>(__VA_ARGS__)
+#define LOVASZ_LAUNCH CCNET_LAUNCH

@@ -3,25 +3,13 @@
 #include "ccnet_ohem.h"
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "ohem_kernels.hpp"
 
+#define CCNET_ERROR_PREFIX "ccnet_ohem: "
+#include "../csrc_common/ccnet_host.hpp"
+
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    int n = snprintf(g_err, sizeof g_err, "ccnet_ohem: ");
-    vsnprintf(g_err + n, sizeof g_err - n, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
 // scipy.ndimage.zoom's output length round(n * (1 / factor)) (ties to even) and its grid_mode=False source step
 int zoom_len(int n, int factor) { return (int)nearbyint(n * (1.0 / factor)); }
@@ -49,15 +37,6 @@ bool layout(int B, int C, int H, int W, int factor, Layout &L) {
     L.scalars = o;  o += align256(sizeof(ohem::Scalars));
     L.total = o;
     return true;
-}
-
-template <class T>
-T *at(void *ws, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(ws) + off); }
-
-int launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, "%s launch failed: %s", what, hipGetErrorString(e));
-    return 0;
 }
 
 unsigned blocks(int n, int per) { return (unsigned)((n + per - 1) / per); }

@@ -1,11 +1,9 @@
 // abn_platform.hpp (tests/emu_abn) -- SIMT-emulator implementations of the device primitives of
-// ccnet_amd/csrc_abn/abn_platform.hpp, on top of the shared emulator in tests/emu/.  Test infrastructure only: the emulator
-// build of the ABN kernels puts this directory FIRST on the include path; the product build never does.
+// ccnet_amd/csrc_abn/abn_platform.hpp, on top of the shared emulator in tests/emu/ and the shared primitives of
+// tests/emu_common/.  Test infrastructure only: the emulator build of the ABN kernels puts this directory FIRST on the include
+// path; the product build never does.
 #pragma once
-#include "hip_emu.hpp"
-
-#include <stdint.h>
-#include <string.h>
+#include "../emu_common/ccnet_device.hpp"
 
 struct uint4 {
     uint32_t x, y, z, w;
@@ -13,22 +11,9 @@ struct uint4 {
 
 namespace abn {
 
-constexpr int kWave = 64;
-
-__device__ inline int lane_id() { return emu::lane_id(); }
-
-// the same butterfly as the device's __shfl_xor tree, so the emulated sums round exactly like the device's
-__device__ inline double wave_sum(double v) {
-    for (int m = kWave / 2; m > 0; m >>= 1) {
-        uint64_t mine;
-        memcpy(&mine, &v, 8);
-        const uint64_t *s = emu::wave_exchange(mine);
-        double other;
-        memcpy(&other, &s[emu::lane_id() ^ m], 8);
-        v += other;
-    }
-    return v;
-}
+using ccnet_common::kWave;
+using ccnet_common::lane_id;
+using ccnet_common::wave_sum;
 
 __device__ inline uint4 load16(const void *p) {
     if (reinterpret_cast<uintptr_t>(p) & 15) abort();          // the device load needs the alignment the caller promised
@@ -43,4 +28,4 @@ __device__ inline void store16(void *p, uint4 v) {
 
 }  // namespace abn
 
-#define ABN_LAUNCH(kern, grid, block, stream, ...) emu::launch((grid), (block), [&]() { kern(__VA_ARGS__); })
+#define ABN_LAUNCH CCNET_LAUNCH

@@ -1,37 +1,18 @@
-// ohem_platform.hpp (tests/emu_ohem) -- SIMT-emulator implementations of the device primitives of
-// ccnet_amd/csrc_ohem/ohem_platform.hpp, on top of the shared emulator in tests/emu/.  Test infrastructure only: the
-// emulator build of the OHEM kernels puts this directory FIRST on the include path; the product build never does.
+// ohem_platform.hpp (tests/emu_ohem) -- the emulator twin of ccnet_amd/csrc_ohem/ohem_platform.hpp: the same names, taken from
+// the emulated primitives of tests/emu_common/ccnet_device.hpp.  Test infrastructure only: the emulator build of the OHEM
+// kernels puts this directory FIRST on the include path; the product build never does.
 #pragma once
-#include "hip_emu.hpp"
+#include "../emu_common/ccnet_device.hpp"
 
 #include <math.h>
-#include <stdint.h>
-#include <string.h>
 
 namespace ohem {
 
-constexpr int kWave = 64;
-
-__device__ inline int lane_id() { return emu::lane_id(); }
-
-// the same butterfly as the device's __shfl_xor tree, so the emulated sums round exactly like the device's
-template <class T>
-__device__ inline T wave_sum(T v) {
-    static_assert(sizeof(T) <= 8, "one 64-bit payload per lane");
-    for (int m = kWave / 2; m > 0; m >>= 1) {
-        uint64_t mine = 0;
-        memcpy(&mine, &v, sizeof(T));
-        const uint64_t *s = emu::wave_exchange(mine);
-        T other;
-        memcpy(&other, &s[emu::lane_id() ^ m], sizeof(T));
-        v += other;
-    }
-    return v;
-}
-
-// fibers switch only at barriers and collectives, so a plain increment is atomic here
-__device__ inline void lds_inc(unsigned *p) { *p += 1u; }
+using ccnet_common::kWave;
+using ccnet_common::lane_id;
+using ccnet_common::lds_inc;
+using ccnet_common::wave_sum;
 
 }  // namespace ohem
 
-#define OHEM_LAUNCH(kern, grid, block, stream, ...) emu::launch((grid), (block), [&]() { kern(__VA_ARGS__); })
+#define OHEM_LAUNCH CCNET_LAUNCH

@@ -5,37 +5,22 @@ for the host against tests/emu/cca_platform.hpp), so the tests drive it through 
 buffers standing in for device memory.  Test infrastructure only.
 """
 import os
-import subprocess
 
 import numpy as np
 
 from ccnet_amd._lib import CCNET_CA_ENERGY, CCNET_CA_SOFTMAX, CcaLibrary
+from lib_checks import INCLUDE, build_emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 CSRC = os.path.join(ROOT, "ccnet_amd", "csrc")
 EMU_LIB = os.path.join(EMU_DIR, "libcca_emu.so")
-HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
-
-
-def _sources():
-    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp", "cca_platform.hpp", "cca_emu_tu.cpp")]
-    srcs += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs.append(os.path.join(ROOT, "include", "ccnet_cca.h"))
-    return srcs
 
 
 def build_emu(force=False):
-    cxx = HOST_CXX if os.path.exists(HOST_CXX) else "g++"
-    if not force and os.path.exists(EMU_LIB):
-        if os.path.getmtime(EMU_LIB) >= max(os.path.getmtime(s) for s in _sources()):
-            return EMU_LIB
-    cmd = [cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
-           "-I" + EMU_DIR, "-I" + CSRC,          # tests/emu FIRST: <cca_platform.hpp> resolves to the emulator's
-           os.path.join(EMU_DIR, "cca_emu_tu.cpp"),   # cca_api.hip, with counted barriers charged to their callers' lines
-           os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB]
-    subprocess.run(cmd, check=True, cwd=ROOT)
-    return EMU_LIB
+    # tests/emu FIRST: <cca_platform.hpp> resolves to the emulator's; cca_emu_tu.cpp is cca_api.hip, with counted barriers
+    # charged to their callers' lines
+    return build_emu_library(EMU_LIB, os.path.join(EMU_DIR, "cca_emu_tu.cpp"), [EMU_DIR, CSRC, INCLUDE], force=force)
 
 
 def _p(a):

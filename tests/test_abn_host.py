@@ -4,21 +4,16 @@ tests/emu_abn/) against the float64 oracle of tests/abn_oracle.py."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import abn_cases as K
 import abn_oracle as O
+import lib_checks as L
 from conftest import ROOT
 
 ABN_CSRC = os.path.join(ROOT, "ccnet_amd", "csrc_abn")
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU_ABN_DIR = os.path.join(ROOT, "tests", "emu_abn")
-EMU_LIB = os.path.join(EMU_ABN_DIR, "libabn_emu.so")
-HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -36,8 +31,7 @@ def test_library_exports_exactly_the_header(abn_lib_path):
     from ccnet_amd import _abn_lib
     names = _abn_lib.declared_symbols()
     assert set(names) == set(_abn_lib._PROTOTYPES) and len(names) == 9
-    out = subprocess.run(["nm", "-D", "--defined-only", abn_lib_path], capture_output=True, text=True, check=True).stdout
-    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == names
+    assert L.exported_symbols(abn_lib_path) == names
 
 
 def test_library_contains_gfx950_code(abn_lib_path):
@@ -106,40 +100,25 @@ def test_version_and_argument_validation_without_a_gpu(abn_lib_path):
     assert lib.last_error().startswith("ccnet_abn:")
 
 
-def _code_object_kernels(lib_path, tmp_path):
-    fat, co = str(tmp_path / "abn.fatbin"), str(tmp_path / "abn.co")
-    subprocess.run([f"{LLVM_BIN}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
-    subprocess.run([f"{LLVM_BIN}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
-    notes = subprocess.run([f"{LLVM_BIN}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
-        if not m:
-            continue
-        key, val = m.group(1), m.group(2)
-        if key == "name":
-            cur = kernels.setdefault(val, {}) if val.startswith("_ZN3abn") else None
-        elif cur is not None and key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-            cur[key] = int(val)
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/clang-offload-bundler"), reason="no LLVM binutils")
+@pytest.mark.skipif(not L.HAVE_LLVM_BINUTILS, reason="no LLVM binutils")
 def test_no_kernel_uses_scratch(abn_lib_path, tmp_path):
-    kernels = _code_object_kernels(abn_lib_path, tmp_path)
+    kernels = L.code_object_kernels(abn_lib_path, tmp_path, "_ZN3abn")
     assert len(kernels) == 12, sorted(kernels)              # 5 templates x 2 dtypes + 2 per-channel kernels
-    bad = {n: k for n, k in kernels.items() if any(k.get(f, 0) for f in ("private_segment_fixed_size", "vgpr_spill_count",
-                                                                           "sgpr_spill_count"))}
+    bad = L.kernels_using_scratch(kernels)
     assert not bad, bad
 
 
 def test_sources_carry_no_env_knobs_no_emulator_code_and_no_float_atomics():
-    files = [f for f in os.listdir(ABN_CSRC) if f.endswith((".hip", ".hpp"))]
+    files = L.product_sources(ABN_CSRC)
     assert sorted(files) == ["abn_api.hip", "abn_kernels.hpp", "abn_platform.hpp"]
-    for f in files:
-        text = open(os.path.join(ABN_CSRC, f)).read()
+    # of the shared device primitives the ABN sources take the wave size, the lane id and the sum only (not the LDS counter)
+    assert sorted(re.findall(r"ccnet_common::(\w+)", "".join(files.values()))) == ["kWave", "lane_id", "wave_sum"]
+    common = L.product_sources(L.COMMON_CSRC)
+    assert sorted(common) == ["ccnet_device.hpp", "ccnet_host.hpp"]
+    for f, text in {**files, **common}.items():
         assert "getenv" not in text and "CCNET_EMU" not in text and "hip_emu" not in text and "emu::" not in text, f
+        if f == "ccnet_device.hpp":                 # (the shared header's LDS integer increment, which ABN does not take)
+            text = text.replace("atomicAdd(p, 1u)", "", 1)
         assert "atomic" not in text.lower(), f
         assert "__fdividef" not in text and "fast-math" not in text and "hipDeviceSynchronize" not in text, f
         assert "hipStreamSynchronize" not in text and "hipMemcpy" not in text, f
@@ -209,24 +188,10 @@ def test_driver_flags():
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernel sources in the SIMT emulator
 # ---------------------------------------------------------------------------------------------------------------------
-def _emu_sources():
-    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp")]
-    srcs += [os.path.join(EMU_ABN_DIR, "abn_platform.hpp"), os.path.join(ROOT, "include", "ccnet_abn.h")]
-    srcs += [os.path.join(ABN_CSRC, f) for f in os.listdir(ABN_CSRC) if f.endswith((".hip", ".hpp"))]
-    return srcs
-
-
 @pytest.fixture(scope="module")
 def emu():
     from ccnet_amd._abn_lib import AbnLibrary
-    stale = not os.path.exists(EMU_LIB) or os.path.getmtime(EMU_LIB) < max(os.path.getmtime(s) for s in _emu_sources())
-    if stale:
-        cxx = HOST_CXX if os.path.exists(HOST_CXX) else "g++"
-        subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
-                        "-I" + EMU_ABN_DIR, "-I" + EMU_DIR, "-I" + ABN_CSRC, "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ABN_CSRC, "abn_api.hip"), os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB],
-                       check=True, cwd=ROOT)
-    return AbnLibrary(EMU_LIB)
+    return AbnLibrary(L.build_shared_scaffold_emu("abn"))
 
 
 def emu_abn(lib, x, weight, bias, rm, rv, dy, **kw):

@@ -3,7 +3,6 @@ tests/emu_proj/ (the emulator twins of the platform headers, first on the includ
 the device library on numpy buffers.  The case table and its bars live in tests/proj_cases.py; tests/test_gpu_proj.py runs the
 same table on the device."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -14,25 +13,17 @@ if HERE not in sys.path:
 
 import proj_cases as K  # noqa: E402
 from guarded_memory import HostMemory  # noqa: E402
+from lib_checks import INCLUDE, build_emu_library  # noqa: E402
 
 ROOT = os.path.dirname(HERE)
 EMU_DIR, EMU_PROJ_DIR = os.path.join(HERE, "emu"), os.path.join(HERE, "emu_proj")
 CSRC, PROJ_CSRC = os.path.join(ROOT, "ccnet_amd", "csrc"), os.path.join(ROOT, "ccnet_amd", "csrc_proj")
 EMU_LIB = os.path.join(EMU_PROJ_DIR, "libproj_emu.so")
-HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
 
 
 def build_emu():
-    srcs = [os.path.join(d, f) for d in (EMU_DIR, EMU_PROJ_DIR, CSRC, PROJ_CSRC) for f in os.listdir(d)
-            if f.endswith((".hip", ".hpp", ".cpp"))] + [os.path.join(ROOT, "include", "ccnet_proj.h")]
-    if os.path.exists(EMU_LIB) and os.path.getmtime(EMU_LIB) >= max(os.path.getmtime(s) for s in srcs):
-        return EMU_LIB
-    cxx = HOST_CXX if os.path.exists(HOST_CXX) else "g++"
-    cmd = [cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
-           "-I" + EMU_DIR, "-I" + EMU_PROJ_DIR, "-I" + PROJ_CSRC, "-I" + CSRC,     # the emulator's headers FIRST
-           os.path.join(PROJ_CSRC, "proj_api.hip"), os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB]
-    subprocess.run(cmd, check=True, cwd=ROOT)
-    return EMU_LIB
+    return build_emu_library(EMU_LIB, os.path.join(PROJ_CSRC, "proj_api.hip"),
+                             [EMU_DIR, EMU_PROJ_DIR, PROJ_CSRC, CSRC, INCLUDE])            # the emulator's headers FIRST
 
 
 @pytest.fixture(scope="module")

@@ -5,25 +5,19 @@ the rank sharding and the confusion reduction over gloo."""
 import ctypes
 import glob
 import os
-import re
 import socket
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import lib_checks as L
 import eval_oracle as O
 from conftest import GOLDEN, ROOT
 
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "eval_*.npz")))
 SMALL = [f for f in FIXTURES if "recipe" not in f]
 EVAL_CSRC = os.path.join(ROOT, "ccnet_amd", "csrc_eval")
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU_EVAL_DIR = os.path.join(ROOT, "tests", "emu_eval")
-EMU_LIB = os.path.join(EMU_EVAL_DIR, "libeval_emu.so")
-HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 
 
 def _id(path):
@@ -95,8 +89,7 @@ def test_library_exports_exactly_the_header(eval_lib_path):
     from ccnet_amd import _eval_lib
     names = _eval_lib.declared_symbols()
     assert set(names) == set(_eval_lib._PROTOTYPES) and len(names) == 4
-    out = subprocess.run(["nm", "-D", "--defined-only", eval_lib_path], capture_output=True, text=True, check=True).stdout
-    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == names
+    assert L.exported_symbols(eval_lib_path) == names
 
 
 def test_library_contains_gfx950_code(eval_lib_path):
@@ -104,31 +97,11 @@ def test_library_contains_gfx950_code(eval_lib_path):
     assert b"gfx950" in blob and b"sliding_kernel" in blob
 
 
-def _code_object_kernels(lib_path, tmp_path):
-    fat, co = str(tmp_path / "eval.fatbin"), str(tmp_path / "eval.co")
-    subprocess.run([f"{LLVM_BIN}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
-    subprocess.run([f"{LLVM_BIN}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
-    notes = subprocess.run([f"{LLVM_BIN}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
-        if not m:
-            continue
-        key, val = m.group(1), m.group(2)
-        if key == "name":
-            cur = kernels.setdefault(val, {}) if val.startswith("_ZN7segeval") else None
-        elif cur is not None and key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-            cur[key] = int(val)
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/clang-offload-bundler"), reason="no LLVM binutils")
+@pytest.mark.skipif(not L.HAVE_LLVM_BINUTILS, reason="no LLVM binutils")
 def test_no_kernel_uses_scratch(eval_lib_path, tmp_path):
-    kernels = _code_object_kernels(eval_lib_path, tmp_path)
+    kernels = L.code_object_kernels(eval_lib_path, tmp_path, "_ZN7segeval")
     assert len(kernels) == 1, sorted(kernels)
-    bad = {n: k for n, k in kernels.items() if any(k.get(f, 0) for f in ("private_segment_fixed_size", "vgpr_spill_count",
-                                                                           "sgpr_spill_count"))}
+    bad = L.kernels_using_scratch(kernels)
     assert not bad, bad
 
 
@@ -161,10 +134,9 @@ def test_version_and_argument_validation_without_a_gpu(eval_lib_path):
 
 
 def test_sources_carry_no_env_knobs_and_no_emulator_code():
-    files = [f for f in os.listdir(EVAL_CSRC) if f.endswith((".hip", ".hpp"))]
-    assert "eval_api.hip" in files and "eval_kernels.hpp" in files
-    for f in files:
-        text = open(os.path.join(EVAL_CSRC, f)).read()
+    files = L.product_sources(EVAL_CSRC, L.COMMON_CSRC)
+    assert "eval_api.hip" in files and "eval_kernels.hpp" in files and "ccnet_host.hpp" in files
+    for f, text in files.items():
         assert "getenv" not in text and "CCNET_EMU" not in text and "hip_emu" not in text and "emu::" not in text, f
 
 
@@ -184,24 +156,10 @@ def test_cpu_input_raises_instead_of_falling_back():
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernel sources in the SIMT emulator
 # ---------------------------------------------------------------------------------------------------------------------
-def _emu_sources():
-    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp")]
-    srcs += [os.path.join(EMU_EVAL_DIR, "eval_platform.hpp"), os.path.join(ROOT, "include", "ccnet_eval.h")]
-    srcs += [os.path.join(EVAL_CSRC, f) for f in os.listdir(EVAL_CSRC) if f.endswith((".hip", ".hpp"))]
-    return srcs
-
-
 @pytest.fixture(scope="module")
 def emu():
     from ccnet_amd._eval_lib import EvalLibrary
-    stale = not os.path.exists(EMU_LIB) or os.path.getmtime(EMU_LIB) < max(os.path.getmtime(s) for s in _emu_sources())
-    if stale:
-        cxx = HOST_CXX if os.path.exists(HOST_CXX) else "g++"
-        subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
-                        "-I" + EMU_EVAL_DIR, "-I" + EMU_DIR, "-I" + EVAL_CSRC, "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(EVAL_CSRC, "eval_api.hip"), os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB],
-                       check=True, cwd=ROOT)
-    return EvalLibrary(EMU_LIB)
+    return EvalLibrary(L.build_shared_scaffold_emu("eval"))
 
 
 def emu_eval(lib, tiles, origins, tile, H, W, flip=False, label=None, C=None, conf=None, ignore_label=255):

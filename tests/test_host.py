@@ -7,6 +7,7 @@ import re
 import pytest
 import torch
 
+import lib_checks as L
 from conftest import ROOT, load_golden
 
 REF_KEYS = {  # state_dict of the reference module (functions.py:19-24) for in_dim = C
@@ -34,9 +35,7 @@ def test_device_library_exports_every_declared_symbol(device_lib_path):
         assert hasattr(dll, n), f"{n} declared in include/ccnet_cca.h but not exported"
     # ... and NOTHING ELSE is a dynamic symbol (align256, find_word_option, softmax_backward_impl and the
     # kernels' device stubs used to sit next to the C ABI): -fvisibility=hidden + csrc/exports.map
-    import subprocess
-    out = subprocess.run(["nm", "-D", "--defined-only", device_lib_path], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
+    exported = L.exported_symbols(device_lib_path)
     assert exported == sorted(names), sorted(set(exported) ^ set(names))
     lib = _lib.CcaLibrary(device_lib_path)
     assert lib.ccnet_cca_version() == 220 and lib.ccnet_cca_arch() == b"gfx950"
@@ -52,7 +51,6 @@ def test_device_library_contains_gfx950_code_object(device_lib_path):
     assert b"gfx950" in blob and b"weight_strip_kernel" in blob and b"map_strip_kernel" in blob
 
 
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 # kernels that may still use scratch: none of them is on a default route of the headline / configs[4] steps (long-strip
 # windowed kernels); everything else must be spill-free
 SCRATCH_ALLOWED = ("map_long_kernel",)          # the windowed kernels of strips 101 .. 320 (cca_long.hpp): SGPR spills + <= 84 B of scratch
@@ -60,38 +58,14 @@ SCRATCH_ALLOWED = ("map_long_kernel",)          # the windowed kernels of strips
 #  strip kernel -- 36 B of scratch -- left the library)
 
 
-def code_object_kernels(lib_path, tmp_path):
-    """{demangled-ish kernel name: metadata dict} read from the gfx950 code object inside the shipped library."""
-    import subprocess
-    fat, co = str(tmp_path / "cca.fatbin"), str(tmp_path / "cca.co")
-    subprocess.run([f"{LLVM_BIN}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
-    subprocess.run([f"{LLVM_BIN}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
-    notes = subprocess.run([f"{LLVM_BIN}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
-        if not m:
-            continue
-        key, val = m.group(1), m.group(2)
-        if key == "name" and val.startswith("_ZN3cca"):
-            cur = kernels.setdefault(val, {})
-        elif key == "name":
-            cur = None if not val.startswith("_Z") else cur
-        elif cur is not None and key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count"):
-            cur[key] = int(val)
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/clang-offload-bundler"), reason="no LLVM binutils")
+@pytest.mark.skipif(not L.HAVE_LLVM_BINUTILS, reason="no LLVM binutils")
 def test_hot_path_kernels_have_no_scratch_and_no_spilled_vgprs(device_lib_path, tmp_path):
     """0 spilled VGPRs and 0 bytes of scratch in every kernel a default route can reach (read from the
     code-object notes of the library that ships, not from a compiler remark)."""
-    kernels = code_object_kernels(device_lib_path, tmp_path)
+    kernels = L.code_object_kernels(device_lib_path, tmp_path, "_ZN3cca")
     assert len(kernels) > 20
-    bad = {n: k for n, k in kernels.items()
-           if (k.get("private_segment_fixed_size", 0) or k.get("vgpr_spill_count", 0))
-           and not any(a in n for a in SCRATCH_ALLOWED)}
+    bad = {n: k for n, k in L.kernels_using_scratch(kernels, ("private_segment_fixed_size", "vgpr_spill_count")).items()
+           if not any(a in n for a in SCRATCH_ALLOWED)}
     assert not bad, bad
 
 

@@ -4,23 +4,17 @@ themselves run in the SIMT emulator (tests/emu/ + the Lovász primitives of test
 import ctypes
 import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import lib_checks as L
 import lovasz_oracle as O
 from conftest import GOLDEN, ROOT
 
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "lovasz_[0-9]*.npz")))
 CRITERION_FIXTURE = os.path.join(GOLDEN, "lovasz_criterion_1x19x97x97_769.npz")
 LOVASZ_CSRC = os.path.join(ROOT, "ccnet_amd", "csrc_lovasz")
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU_LOVASZ_DIR = os.path.join(ROOT, "tests", "emu_lovasz")
-EMU_LIB = os.path.join(EMU_LOVASZ_DIR, "liblovasz_emu.so")
-HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 TILE = 2048                     # lovasz::kTile: sorted positions per workgroup of every sort and scan pass
 
 
@@ -83,8 +77,7 @@ def test_library_exports_exactly_the_header(lovasz_lib_path):
     from ccnet_amd import _lovasz_lib
     names = _lovasz_lib.declared_symbols()
     assert set(names) == set(_lovasz_lib._PROTOTYPES) and len(names) == 6
-    out = subprocess.run(["nm", "-D", "--defined-only", lovasz_lib_path], capture_output=True, text=True, check=True).stdout
-    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == names
+    assert L.exported_symbols(lovasz_lib_path) == names
 
 
 def test_library_contains_gfx950_code(lovasz_lib_path):
@@ -132,43 +125,22 @@ def test_class_selection_argument():
         class_selection("some", 5)
 
 
-def _code_object_kernels(lib_path, tmp_path):
-    fat, co = str(tmp_path / "lovasz.fatbin"), str(tmp_path / "lovasz.co")
-    subprocess.run([f"{LLVM_BIN}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
-    subprocess.run([f"{LLVM_BIN}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
-    notes = subprocess.run([f"{LLVM_BIN}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
-        if not m:
-            continue
-        key, val = m.group(1), m.group(2)
-        if key == "name":
-            cur = kernels.setdefault(val, {}) if val.startswith("_ZN6lovasz") else None
-        elif cur is not None and key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-            cur[key] = int(val)
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/clang-offload-bundler"), reason="no LLVM binutils")
+@pytest.mark.skipif(not L.HAVE_LLVM_BINUTILS, reason="no LLVM binutils")
 def test_no_kernel_uses_scratch(lovasz_lib_path, tmp_path):
-    kernels = _code_object_kernels(lovasz_lib_path, tmp_path)
+    kernels = L.code_object_kernels(lovasz_lib_path, tmp_path, "_ZN6lovasz")
     assert len(kernels) == 9, sorted(kernels)
-    bad = {n: k for n, k in kernels.items() if any(k.get(f, 0) for f in ("private_segment_fixed_size", "vgpr_spill_count",
-                                                                           "sgpr_spill_count"))}
+    bad = L.kernels_using_scratch(kernels)
     assert not bad, bad
 
 
 def test_sources_carry_no_env_knobs_no_emulator_code_and_no_float_atomics():
-    files = [f for f in os.listdir(LOVASZ_CSRC) if f.endswith((".hip", ".hpp"))]
-    assert "lovasz_api.hip" in files
-    for f in files:
-        text = open(os.path.join(LOVASZ_CSRC, f)).read()
+    files = L.product_sources(LOVASZ_CSRC, L.COMMON_CSRC)
+    assert "lovasz_api.hip" in files and "ccnet_device.hpp" in files and "ccnet_host.hpp" in files
+    for f, text in files.items():
         assert "getenv" not in text and "CCNET_EMU" not in text and "hip_emu" not in text and "emu::" not in text, f
         assert "__fdividef" not in text and "fast-math" not in text and "hipDeviceSynchronize" not in text, f
         assert "hipStreamSynchronize" not in text and "hipMemcpy" not in text, f
-    platform = open(os.path.join(LOVASZ_CSRC, "lovasz_platform.hpp")).read()
+    platform = files["lovasz_platform.hpp"] + files["ccnet_device.hpp"]             # its own primitives + the shared ones
     assert platform.count("atomicAdd(") == 1 and "atomicAdd(p, 1u)" in platform       # the LDS integer increment only
 
 
@@ -201,24 +173,10 @@ def test_train_driver_flags():
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernel sources in the SIMT emulator
 # ---------------------------------------------------------------------------------------------------------------------
-def _emu_sources():
-    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp")]
-    srcs += [os.path.join(EMU_LOVASZ_DIR, "lovasz_platform.hpp"), os.path.join(ROOT, "include", "ccnet_lovasz.h")]
-    srcs += [os.path.join(LOVASZ_CSRC, f) for f in os.listdir(LOVASZ_CSRC) if f.endswith((".hip", ".hpp"))]
-    return srcs
-
-
 @pytest.fixture(scope="module")
 def emu():
     from ccnet_amd._lovasz_lib import LovaszLibrary
-    stale = not os.path.exists(EMU_LIB) or os.path.getmtime(EMU_LIB) < max(os.path.getmtime(s) for s in _emu_sources())
-    if stale:
-        cxx = HOST_CXX if os.path.exists(HOST_CXX) else "g++"
-        subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
-                        "-I" + EMU_LOVASZ_DIR, "-I" + EMU_DIR, "-I" + LOVASZ_CSRC, "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(LOVASZ_CSRC, "lovasz_api.hip"), os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB],
-                       check=True, cwd=ROOT)
-    return LovaszLibrary(EMU_LIB)
+    return LovaszLibrary(L.build_shared_scaffold_emu("lovasz"))
 
 
 def emu_lovasz(lib, probas, labels, classes="present", per_image=False, ignore=None, grad_out=1.0):

@@ -4,23 +4,17 @@ the SIMT emulator (tests/emu/ + the OHEM primitives of tests/emu_ohem/) against 
 import ctypes
 import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import lib_checks as L
 import ohem_oracle as O
 from conftest import GOLDEN, ROOT
 
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "ohem_*.npz")))
 SMALL = [f for f in FIXTURES if "769x769" not in f]
 OHEM_CSRC = os.path.join(ROOT, "ccnet_amd", "csrc_ohem")
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU_OHEM_DIR = os.path.join(ROOT, "tests", "emu_ohem")
-EMU_LIB = os.path.join(EMU_OHEM_DIR, "libohem_emu.so")
-HOST_CXX = "/opt/rocm/lib/llvm/bin/clang++"
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 
 
 def _id(path):
@@ -72,8 +66,7 @@ def test_library_exports_exactly_the_header(ohem_lib_path):
     from ccnet_amd import _ohem_lib
     names = _ohem_lib.declared_symbols()
     assert set(names) == set(_ohem_lib._PROTOTYPES) and len(names) == 6
-    out = subprocess.run(["nm", "-D", "--defined-only", ohem_lib_path], capture_output=True, text=True, check=True).stdout
-    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == names
+    assert L.exported_symbols(ohem_lib_path) == names
 
 
 def test_library_contains_gfx950_code(ohem_lib_path):
@@ -102,63 +95,28 @@ def test_version_and_argument_validation_without_a_gpu(ohem_lib_path):
     assert lib.last_error().startswith("ccnet_ohem:")
 
 
-def _code_object_kernels(lib_path, tmp_path):
-    fat, co = str(tmp_path / "ohem.fatbin"), str(tmp_path / "ohem.co")
-    subprocess.run([f"{LLVM_BIN}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
-    subprocess.run([f"{LLVM_BIN}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
-    notes = subprocess.run([f"{LLVM_BIN}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
-        if not m:
-            continue
-        key, val = m.group(1), m.group(2)
-        if key == "name":
-            cur = kernels.setdefault(val, {}) if val.startswith("_ZN4ohem") else None
-        elif cur is not None and key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-            cur[key] = int(val)
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/clang-offload-bundler"), reason="no LLVM binutils")
+@pytest.mark.skipif(not L.HAVE_LLVM_BINUTILS, reason="no LLVM binutils")
 def test_no_kernel_uses_scratch(ohem_lib_path, tmp_path):
-    kernels = _code_object_kernels(ohem_lib_path, tmp_path)
+    kernels = L.code_object_kernels(ohem_lib_path, tmp_path, "_ZN4ohem")
     assert len(kernels) == 5, sorted(kernels)
-    bad = {n: k for n, k in kernels.items() if any(k.get(f, 0) for f in ("private_segment_fixed_size", "vgpr_spill_count",
-                                                                           "sgpr_spill_count"))}
+    bad = L.kernels_using_scratch(kernels)
     assert not bad, bad
 
 
 def test_sources_carry_no_env_knobs_and_no_emulator_code():
-    files = [f for f in os.listdir(OHEM_CSRC) if f.endswith((".hip", ".hpp"))]
-    assert "ohem_api.hip" in files
-    for f in files:
-        text = open(os.path.join(OHEM_CSRC, f)).read()
+    files = L.product_sources(OHEM_CSRC, L.COMMON_CSRC)
+    assert "ohem_api.hip" in files and "ccnet_device.hpp" in files and "ccnet_host.hpp" in files
+    for f, text in files.items():
         assert "getenv" not in text and "CCNET_EMU" not in text and "hip_emu" not in text and "emu::" not in text, f
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernel sources in the SIMT emulator
 # ---------------------------------------------------------------------------------------------------------------------
-def _emu_sources():
-    srcs = [os.path.join(EMU_DIR, f) for f in ("hip_emu.cpp", "hip_emu.hpp")]
-    srcs += [os.path.join(EMU_OHEM_DIR, "ohem_platform.hpp"), os.path.join(ROOT, "include", "ccnet_ohem.h")]
-    srcs += [os.path.join(OHEM_CSRC, f) for f in os.listdir(OHEM_CSRC) if f.endswith((".hip", ".hpp"))]
-    return srcs
-
-
 @pytest.fixture(scope="module")
 def emu():
     from ccnet_amd._ohem_lib import OhemLibrary
-    stale = not os.path.exists(EMU_LIB) or os.path.getmtime(EMU_LIB) < max(os.path.getmtime(s) for s in _emu_sources())
-    if stale:
-        cxx = HOST_CXX if os.path.exists(HOST_CXX) else "g++"
-        subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-pass-failed",
-                        "-I" + EMU_OHEM_DIR, "-I" + EMU_DIR, "-I" + OHEM_CSRC, "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(OHEM_CSRC, "ohem_api.hip"), os.path.join(EMU_DIR, "hip_emu.cpp"), "-o", EMU_LIB],
-                       check=True, cwd=ROOT)
-    return OhemLibrary(EMU_LIB)
+    return OhemLibrary(L.build_shared_scaffold_emu("ohem"))
 
 
 def emu_ohem(lib, logits, target, ignore_label=255, thresh=0.7, min_kept=100000, factor=8, grad_out=1.0):

@@ -3,15 +3,13 @@ symbol set, the gfx950 code object and its resource metadata, argument validatio
 no device), the row planner and the routing table."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
+import lib_checks as L
 from conftest import ROOT
 
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 KERNELS = ("gemm_bf16_kernel", "pack_kernel", "colsum_slab_kernel", "colsum_finish_kernel")
 
 
@@ -34,8 +32,7 @@ def test_build_produces_the_library_with_exactly_the_declared_symbols(lib_path, 
     from ccnet_amd import _proj_lib
     names = _proj_lib.declared_symbols()
     assert len(names) == 7 and set(names) == set(_proj_lib._PROTOTYPES)
-    out = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
+    exported = L.exported_symbols(lib_path)
     assert exported == sorted(names), sorted(set(exported) ^ set(names))
     assert lib.ccnet_proj_version() == _proj_lib.CCNET_PROJ_VERSION == 100 and lib.ccnet_proj_arch() == b"gfx950"
 
@@ -43,8 +40,7 @@ def test_build_produces_the_library_with_exactly_the_declared_symbols(lib_path, 
 def test_build_leaves_the_attention_library_alone(lib_path):
     """a library of its own: nothing of it is a symbol of libccnet_cca.so, whose sources it only reads"""
     from ccnet_amd import _lib
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "ccnet_proj" not in out
+    assert not any("ccnet_proj" in name for name in L.exported_symbols(_lib.LIB_PATH))
     import __graft_entry__ as g
     assert g.PROJ_LIB == lib_path and g.PROJ_CSRC not in g.HIPCC_FLAGS
 
@@ -56,32 +52,9 @@ def test_library_contains_the_gfx950_kernels(lib_path):
         assert k.encode() in blob, k
 
 
-def code_object_kernels(lib_path, tmp_path, prefix="_ZN4proj"):
-    """{mangled kernel name: metadata dict} read from the gfx950 code object inside the shipped library (the reading method of
-    tests/test_host.py::code_object_kernels, for this library's namespace)."""
-    fat, co = str(tmp_path / "proj.fatbin"), str(tmp_path / "proj.co")
-    subprocess.run([f"{LLVM_BIN}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
-    subprocess.run([f"{LLVM_BIN}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
-    notes = subprocess.run([f"{LLVM_BIN}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
-        if not m:
-            continue
-        key, val = m.group(1), m.group(2)
-        if key == "name" and val.startswith(prefix):
-            cur = kernels.setdefault(val, {})
-        elif key == "name":
-            cur = None if not val.startswith("_Z") else cur
-        elif cur is not None and key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count"):
-            cur[key] = int(val)
-    return kernels
-
-
 def test_new_kernels_have_no_scratch_and_no_spilled_vgprs(lib_path, tmp_path):
-    assert os.path.exists(f"{LLVM_BIN}/clang-offload-bundler"), "the LLVM binutils of the ROCm installation are needed"
-    kernels = code_object_kernels(lib_path, tmp_path)
+    assert L.HAVE_LLVM_BINUTILS, "the LLVM binutils of the ROCm installation are needed"
+    kernels = L.code_object_kernels(lib_path, tmp_path, "_ZN4proj")
     for k in KERNELS:
         assert any(k in n for n in kernels), (k, sorted(kernels))
     assert sum("gemm_bf16_kernel" in n for n in kernels) == 2              # with and without the K tail
