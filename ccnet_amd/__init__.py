@@ -6,6 +6,7 @@ ctypes binding (:mod:`ccnet_amd._lib`) and the host-side mirror of the reference
 device library; the first kernel call does, and fails loudly if it has not been built.
 """
 from .abn import ABN, InPlaceABN, InPlaceABNSync, convert_abn
+from .dsn import UpsampledCrossEntropy2d, UpsampledCrossEntropyFunction
 from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFunction, INF, ca_map, ca_softmax,
                         ca_weight, criss_cross_attention, graph_module)
 from .evaluate import SegEvaluator, predict_sliding, predict_whole
@@ -15,5 +16,6 @@ from .ohem import CriterionOhemDSN, OhemCrossEntropy2d
 __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "ca_weight", "ca_map",
            "ca_softmax", "criss_cross_attention", "graph_module", "INF", "OhemCrossEntropy2d", "CriterionOhemDSN",
            "SegEvaluator", "predict_sliding", "predict_whole", "lovasz_softmax", "LovaszSoftmax", "LovaszSoftmaxFunction",
-           "CriterionOhemDSN2", "ABN", "InPlaceABN", "InPlaceABNSync", "convert_abn"]
+           "CriterionOhemDSN2", "ABN", "InPlaceABN", "InPlaceABNSync", "convert_abn", "UpsampledCrossEntropy2d",
+           "UpsampledCrossEntropyFunction"]
 __version__ = "0.1.0"

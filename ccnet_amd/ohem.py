@@ -91,16 +91,28 @@ class OhemCrossEntropy2d(nn.Module):
 
 class CriterionOhemDSN(nn.Module):
     """OHEM cross-entropy on the up-sampled main logits + 0.4 x cross-entropy on the up-sampled DSN logits
-    (loss/criterion.py:37-56).  The bilinear up-sampling stays a stock op, as in the reference."""
+    (loss/criterion.py:37-56).  The bilinear up-sampling stays a stock op, as in the reference; with ``fused_aux=True`` the
+    second, plain cross-entropy head runs on :class:`ccnet_amd.dsn.UpsampledCrossEntropy2d` instead, which up-samples
+    inside its kernels (the OHEM head needs the full-resolution map for its threshold search and keeps the stock op)."""
 
-    def __init__(self, ignore_index=255, thresh=0.7, min_kept=100000, use_weight=True, reduction="mean"):
+    def __init__(self, ignore_index=255, thresh=0.7, min_kept=100000, use_weight=True, reduction="mean", fused_aux=False):
         super().__init__()
         self.ignore_index = ignore_index
+        self.fused_aux = bool(fused_aux)
         self.criterion1 = OhemCrossEntropy2d(ignore_index, thresh, min_kept)
-        self.criterion2 = nn.CrossEntropyLoss(ignore_index=ignore_index, reduction=reduction)
+        if self.fused_aux:
+            if reduction != "mean":
+                raise ValueError(f"CriterionOhemDSN(fused_aux=True): only reduction='mean' runs on the device kernels, got {reduction!r}")
+            from .dsn import UpsampledCrossEntropy2d
+            self.criterion2 = UpsampledCrossEntropy2d(ignore_index)
+        else:
+            self.criterion2 = nn.CrossEntropyLoss(ignore_index=ignore_index, reduction=reduction)
 
     def forward(self, preds, target):
         h, w = target.size(1), target.size(2)
         loss1 = self.criterion1(F.interpolate(preds[0], size=(h, w), mode="bilinear", align_corners=True), target)
-        loss2 = self.criterion2(F.interpolate(preds[1], size=(h, w), mode="bilinear", align_corners=True), target)
+        if self.fused_aux:
+            loss2 = self.criterion2(preds[1], target)
+        else:
+            loss2 = self.criterion2(F.interpolate(preds[1], size=(h, w), mode="bilinear", align_corners=True), target)
         return loss1 + loss2 * 0.4

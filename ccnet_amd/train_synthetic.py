@@ -7,6 +7,8 @@ the same training step on random data, one process per GPU:
     model      ccnet_amd.segmodel.Seg_Model(19, CriterionDSN(), recurrence=2)       train.py:160-164
                --ohem: CriterionOhemDSN(thresh=--ohem-thres, min_kept=--ohem-keep)   train.py:117-122,168-171
                --lovasz: CriterionOhemDSN2 (CE + Lovász-softmax, DSN head unused)   loss/criterion.py:59-78
+               --fused-dsn: ccnet_amd.dsn.CriterionDSN (the up-sample inside the loss kernels); with --ohem,
+               CriterionOhemDSN(fused_aux=True); refused with --lovasz
                --abn device|inplace: every inplace_abn layer swapped for its HIP twin (ccnet_amd.abn.convert_abn)
     data       images randn(b,3,769,769), labels randint(0,19) with ~5 % set to 255 train.py:28-33 (crop 769)
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
@@ -45,6 +47,7 @@ def synthetic_batch(batch, size, num_classes, device, generator):
 def run(args, model_factory=None, quiet=False):
     """One training job on the calling rank; returns the result dict (rank 0) or None.  ``quiet`` suppresses the
     JSON line (bench.py embeds the result in its own line)."""
+    check_args(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -65,10 +68,14 @@ def run(args, model_factory=None, quiet=False):
 
     if model_factory is None:
         from .segmodel import CriterionDSN, CriterionOhemDSN, CriterionOhemDSN2, Seg_Model
+        fused_dsn = getattr(args, "fused_dsn", False)
         if getattr(args, "lovasz", False):
             criterion = CriterionOhemDSN2()
         elif getattr(args, "ohem", False):
-            criterion = CriterionOhemDSN(thresh=args.ohem_thres, min_kept=args.ohem_keep)
+            criterion = CriterionOhemDSN(thresh=args.ohem_thres, min_kept=args.ohem_keep, fused_aux=fused_dsn)
+        elif fused_dsn:
+            from .dsn import CriterionDSN as FusedCriterionDSN
+            criterion = FusedCriterionDSN()
         else:
             criterion = CriterionDSN()
         model = Seg_Model(args.num_classes, criterion=criterion, recurrence=args.recurrence)
@@ -79,7 +86,7 @@ def run(args, model_factory=None, quiet=False):
         from .abn import convert_abn
         convert_abn(model, abn_mode)
     model = model.to(device).train()
-    if use_cuda and abn_mode is not None:
+    if use_cuda and (abn_mode is not None or getattr(args, "fused_dsn", False)):
         torch.cuda.reset_peak_memory_stats(device)
     net = model
     if ddp:
@@ -144,6 +151,10 @@ def run(args, model_factory=None, quiet=False):
             result["criterion"] = "ohem"
         if getattr(args, "lovasz", False):
             result["criterion"] = "lovasz"
+        if getattr(args, "fused_dsn", False):
+            result["criterion"] = "ohem+dsn-fused" if getattr(args, "ohem", False) else "dsn-fused"
+            if use_cuda:
+                result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
         if abn_mode is not None:
             result["abn"] = abn_mode
             result["step_losses"] = [round(float(v.float().item()), 6) for v in losses]
@@ -177,6 +188,11 @@ def build_parser():
                                                           "train.py --ohem True")
     crit.add_argument("--lovasz", action="store_true", help="train with CriterionOhemDSN2: cross-entropy + Lovász-softmax (on the "
                                                             "device) of the main logits, as loss/criterion.py:59-78")
+    ap.add_argument("--fused-dsn", action="store_true",
+                    help="cross-entropy heads that up-sample inside their HIP kernels (ccnet_amd.dsn): the device CriterionDSN, or "
+                         "with --ohem the DSN head of CriterionOhemDSN (fused_aux=True); refused with --lovasz, whose criterion "
+                         "needs the full-resolution map; the JSON line then reports criterion dsn-fused (ohem+dsn-fused) and "
+                         "max_memory_allocated_mb")
     ap.add_argument("--abn", choices=("torch", "device", "inplace"), default=None,
                     help="normalisation layers: torch (the default: the stock inplace_abn restatement), device (the HIP ABN "
                          "kernels, out of place, relu and residual adds fused in the residual units) or inplace (HIP ABN "
@@ -191,5 +207,23 @@ def build_parser():
     return ap
 
 
+def check_args(args):
+    """Combinations the criteria cannot serve; raises ValueError."""
+    if getattr(args, "fused_dsn", False) and getattr(args, "lovasz", False):
+        raise ValueError("--fused-dsn cannot be combined with --lovasz: CriterionOhemDSN2 takes the Lovász-softmax of the "
+                         "full-resolution map and leaves the DSN head unused")
+
+
+def parse_args(argv=None):
+    """build_parser().parse_args with the cross-option checks reported as usage errors."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    try:
+        check_args(args)
+    except ValueError as e:
+        ap.error(str(e))
+    return args
+
+
 if __name__ == "__main__":
-    run(build_parser().parse_args())
+    run(parse_args())
