@@ -53,6 +53,30 @@ std::atomic<int> g_planes_overlap{-1};
 // "planes_xcd" 1 (default): the final NCHW row pass of the split-plane forward decodes its strips from an XCD-aware id (consecutive
 // rows of an image on ONE XCD): the 388-byte NCHW rows of x / y share every boundary line with their neighbour row
 std::atomic<int> g_planes_xcd{1};
+// "cache_order": the order in which the streaming launches of the split-plane step walk the images, so that a launch STARTS on the
+// data its producer touched last -- what is still in the 256 MiB Infinity Cache -- instead of on image 0, which the producer's
+// own later traffic has evicted (each of these launches streams 300-650 MB).  A bit mask, one bit per launch, set = descending:
+//   bit 0  forward column pass     bit 1  forward NCHW row pass     bit 2  dA
+//   bit 3  dv column pass          bit 4  dv row pass
+//   bit 5  the forward NCHW row pass decodes image-major over the XCDs (cca::xcd_image_major_strip) with ASCENDING images; bit 1
+//          selects the same decode, descending -- today's "planes_xcd" decode runs all images at once and has no image order.
+//          Needs what "planes_xcd" needs and B % 8 == 0; otherwise the decode falls back ("planes_xcd" 0: the linear one).
+// 0 = the traversal as it always was, -1 (default) = the shipped pattern kCacheOrderShipped.  The energies, the softmax passes and
+// the dq | dk passes are not in the mask: what they read is under 120 MB and resident in any order; dy -> planes and
+// softmax-backward stay ascending -- the other side of the alternation.  Launches of the bf16 family, of long strips and the
+// three-plane row pass always run ascending.  Read on the host at launch time: a captured graph keeps what was set at capture.
+// Shipped: the forward row pass, dA and the dv column pass descending -- each starts on the image its producer finished, dA and
+// the dv column pass (which run side by side and read the same dy planes) walk together, and the dv row pass and softmax-backward
+// meet their producers' last images going up.  Same-run A/B at (8,512,97,97), graph replay, against mask 0: 0.6701 vs 0.6802 ms
+// over three rounds and 0.6991 vs 0.7104 ms over five on a second box, below mask 0 in every round; the lowest mean of the
+// masks tried (profiles/r07a_ab_cache_order*.txt).
+constexpr int kCacheOrderShipped = 14;
+std::atomic<int> g_cache_order{-1};
+enum { ORDER_L3 = 1, ORDER_L4 = 2, ORDER_L6 = 4, ORDER_L7 = 8, ORDER_L8 = 16, ORDER_L4_XCD = 32 };
+inline int cache_order(int bit) {
+    const int v = g_cache_order.load();
+    return ((v < 0 ? kCacheOrderShipped : v) & bit) ? 1 : 0;
+}
 // "da_stages": ring stages of the persistent dA kernel (plane-free form).  Three fill the CU's LDS (159,744 B): the dv column pass on
 // the side stream could not place a single workgroup next to it and in fact WAITED for the dA workgroups to exit (kernel-trace
 // timeline: its 69 us of work spanned 223 us).  With two stages (106,496 B) one 53,248-byte column workgroup fits per CU and the two
@@ -805,7 +829,7 @@ int launch_gmap_pm(const float *T, const FT *F, const FT *resid, const float *ga
                 // ... and its partial as bf16 (what the reference's bf16 arithmetic rounds out_H / the column half of dv to anyway):
                 // half the bytes of the fp32 partial, written once and read once per pass
                 CCA_LAUNCH((cca::gmap3_kernel<P, false, TRANS, false, 3, 2, bf16_t, bf16_t>), dim3((unsigned)gc.grid), dim3(cca::GS_THREADS), stream,
-                           T, F, (const float *)nullptr, gamma, reinterpret_cast<bf16_t *>(partial), C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split);
+                           T, F, (const float *)nullptr, gamma, reinterpret_cast<bf16_t *>(partial), C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split, 0);
                 if (int e = launch_status("gmap_pm(column, bf16 partial)")) return e;
                 CCA_LAUNCH((cca::gmap_kernel<P, true, TRANS, true, FT, FT, false, false, 2, false, false, true>), dim3((unsigned)gr.grid), dim3(cca::GS_THREADS),
                            stream, T, F, (const float *)partial, resid, gamma, out, C, H, W, fbs, fps, pbs, C, rbs, rps, obs, ops,
@@ -815,7 +839,7 @@ int launch_gmap_pm(const float *T, const FT *F, const FT *resid, const float *ga
         }
         if constexpr (std::is_same<FT, bf16_t>::value)
             CCA_LAUNCH((cca::gmap3_kernel<P, false, TRANS, false, 3, 2, bf16_t>), dim3((unsigned)gc.grid), dim3(cca::GS_THREADS), stream,
-                       T, F, (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split);
+                       T, F, (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split, 0);
     } else {
         CCA_LAUNCH((cca::gmap_kernel<P, false, TRANS, false, FT, float>), dim3((unsigned)gc.grid), dim3(cca::GS_THREADS),
                    stream, T, F, (const float *)nullptr, (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0,
@@ -1113,6 +1137,17 @@ bool plane_layout(int layout, int C, cca::PlaneLayout *pl) {
     else return false;
     return true;
 }
+// The decode of the forward's NCHW row pass under "planes_xcd" and "cache_order" (GmapJob::xcd, ::order): XCD-aware where the
+// strips and the whole rounds divide by 8; image-major over the XCDs where an order bit asks for it and the images divide by
+// 8 too (the rotation of cca::xcd_image_major_strip balances over 8 images), else today's decode, reversed if asked.
+// (``ordered`` false -- rows of 101 .. 132 positions: "planes_xcd" alone.)
+template <typename FT>
+void nchw_row_decode(cca::GmapJob<FT, float> &job, int B, int H, int n_whole, bool ordered = true) {
+    const bool xcd = g_planes_xcd.load() && (B * H) % 8 == 0 && n_whole % 8 == 0;
+    const int desc = ordered ? cache_order(ORDER_L4) : 0;
+    if (xcd) job.xcd = B * H / 8;
+    job.order = desc | (ordered && xcd && B % 8 == 0 && (desc || cache_order(ORDER_L4_XCD)) ? 2 : 0);
+}
 // column strips -> fp32 partial, row strips add it (+ the NCHW residual) and write the output
 // P = 100: column passes on the ring kernel (two slots, three workgroups per CU by default), row passes on gmap_kernel with two
 // workgroups per CU.  P = 132 (strips 101 .. 132): the ring kernel with two slots and two workgroups per CU, the row passes with
@@ -1123,27 +1158,28 @@ int launch_gmap3_planes(const float *T, const bf16p_t *F, const float *gamma, fl
     const long pbs = (long)H * W * C;
     const GmapPlan gr = gmap_plan(B * H, C);
     const int ring = g_planes_ring.load();
+    const int order = cache_order(TRANS ? ORDER_L7 : ORDER_L3);        // (the 100-position column passes; the others run ascending)
     if constexpr (P > 100) {
         const GmapPlan gc = gmap_plan(B * W, C);
         CCA_LAUNCH((cca::gmap3_kernel<P, false, TRANS, false, 2, 2>), dim3((unsigned)gc.grid), dim3(cca::GS_THREADS), stream, T, F,
-                   (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split);
+                   (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split, 0);
         return launch_status("gmap3_planes(column)");
     } else {
     if (ring == 2) {                        // three workgroups per CU, two ring slots
         const GmapPlan gc = gmap_plan(B * W, C, 3);
         CCA_LAUNCH((cca::gmap3_kernel<100, false, TRANS, false, 2, 3>), dim3((unsigned)gc.grid), dim3(cca::GS_THREADS), stream, T, F,
-                   (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split);
+                   (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split, order);
     } else {
         const GmapPlan gc = gmap_plan(B * W, C);
         CCA_LAUNCH((cca::gmap3_kernel<100, false, TRANS, false>), dim3((unsigned)gc.grid), dim3(cca::GS_THREADS), stream, T, F,
-                   (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split);
+                   (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split, order);
     }
     if (int e = launch_status("gmap3_planes(column)")) return e;
     // (row passes: the accumulator-layout addend prefetch of gmap3 is still slower than gmap_kernel's output image --
     // 121 vs 103 us at the headline shape, profiles/r03e_bench.json -- so only "planes_ring" 1 uses it there)
     if (!row_too || ring != 1) return 0;
     CCA_LAUNCH((cca::gmap3_kernel<100, true, TRANS, true>), dim3((unsigned)gr.grid), dim3(cca::GS_THREADS), stream, T, F,
-               (const float *)partial, gamma, out, C, H, W, fbs, fps, pbs, C, obs, ops, gr.n_whole, gr.split);
+               (const float *)partial, gamma, out, C, H, W, fbs, fps, pbs, C, obs, ops, gr.n_whole, gr.split, 0);
     return launch_status("gmap3_planes(row)");
     }
 }
@@ -1155,7 +1191,8 @@ int launch_gmap_planes_row_p(const float *T, const bf16p_t *F, const float *resi
     const long pbs = (long)H * W * C;
     const GmapPlan gr = gmap_plan(B * H, C, WPC);
     cca::GmapJob<bf16p_t, float> job{};
-    if (NCHW && g_planes_xcd.load() && (B * H) % 8 == 0 && gr.n_whole % 8 == 0) job.xcd = B * H / 8;
+    if (NCHW) nchw_row_decode(job, B, H, gr.n_whole, P <= 100 && !TRANS);
+    else if (P <= 100 && TRANS) job.order = cache_order(ORDER_L8);      // (the dv row pass)
     CCA_LAUNCH((cca::gmap_kernel<P, true, TRANS, true, bf16p_t, float, NCHW, false, WPC>), dim3((unsigned)gr.grid), dim3(cca::GS_THREADS),
                stream, T, F, (const float *)partial, resid, gamma, out, C, H, W, fbs, fps, pbs, C, rbs, rps, obs, ops,
                gr.n_whole, gr.split, job);
@@ -1267,10 +1304,10 @@ int launch_gmap_direct_f32(const float *T, const float *v, const float *resid, c
     const long pbs = (long)H * W * C;
     const GmapPlan gc = gmap_plan(B * W, C, 3), gr = gmap_plan(B * H, C, 2);
     CCA_LAUNCH((cca::gmap3_kernel<100, false, false, false, 2, 3, float>), dim3((unsigned)gc.grid), dim3(cca::GS_THREADS), stream, T, v,
-               (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split);
+               (const float *)nullptr, gamma, partial, C, H, W, fbs, fps, 0L, 0, pbs, C, gc.n_whole, gc.split, cache_order(ORDER_L3));
     if (int e = launch_status("gmap3_direct(column)")) return e;
     cca::GmapJob<float, float> job{};
-    if (g_planes_xcd.load() && (B * H) % 8 == 0 && gr.n_whole % 8 == 0) job.xcd = B * H / 8;
+    nchw_row_decode(job, B, H, gr.n_whole);
     CCA_LAUNCH((cca::gmap_kernel<100, true, false, true, float, float, true, false, 2>), dim3((unsigned)gr.grid), dim3(cca::GS_THREADS),
                stream, T, v, (const float *)partial, resid, gamma, out, C, H, W, fbs, fps, pbs, C, rbs, 0, obs, 0,
                gr.n_whole, gr.split, job);
@@ -1647,10 +1684,11 @@ static int backward_planes_impl(const float *dy, const float *q, const float *k,
         // (option values > 1 cap the number of workgroups: tests make one workgroup walk many strips)
         const int nstrips = B * (H + W), cus = ps > 1 ? ps : num_cus();
         const dim3 grid((unsigned)(nstrips < cus ? nstrips : cus)), block(cca::GM_THREADS);
+        const int da_order = cache_order(ORDER_L6);
         if (direct && g_da_stages.load() == 2)
-            CCA_LAUNCH((cca::gweight_stream_kernel<100, bf16p_t, float, 2>), grid, block, stream, dyp, v, scratch, C, B, H, W, dbs, 2 * C, v_bs, v_ps);
-        else if (direct) CCA_LAUNCH((cca::gweight_stream_kernel<100, bf16p_t, float>), grid, block, stream, dyp, v, scratch, C, B, H, W, dbs, 2 * C, v_bs, v_ps);
-        else        CCA_LAUNCH((cca::gweight_stream_kernel<100>), grid, block, stream, dyp, vp, scratch, C, B, H, W, dbs, 2 * C, vp_bs, vp_ps);
+            CCA_LAUNCH((cca::gweight_stream_kernel<100, bf16p_t, float, 2>), grid, block, stream, dyp, v, scratch, C, B, H, W, dbs, 2 * C, v_bs, v_ps, da_order);
+        else if (direct) CCA_LAUNCH((cca::gweight_stream_kernel<100, bf16p_t, float>), grid, block, stream, dyp, v, scratch, C, B, H, W, dbs, 2 * C, v_bs, v_ps, da_order);
+        else        CCA_LAUNCH((cca::gweight_stream_kernel<100>), grid, block, stream, dyp, vp, scratch, C, B, H, W, dbs, 2 * C, vp_bs, vp_ps, da_order);
         e = launch_status("gweight_stream(dA)");
     } else {
         if (direct) return fail(CCNET_E_BADFLAGS, "cca_backward_planes: the plane-free form runs the persistent dA kernel (option planes_stream != 0)");
@@ -1738,6 +1776,7 @@ const OptionRange *find_word_option(const std::string &n) {
         {"planes_stream", &g_planes_stream, 0, 1 << 20},
         {"planes_overlap", &g_planes_overlap, -1, 2},
         {"planes_xcd", &g_planes_xcd, 0, 1},
+        {"cache_order", &g_cache_order, -1, 63},
         {"energy_tail", &g_energy_tail, 0, 1},
         {"dqdk_wpc3", &g_dqdk_wpc3, 0, 1},
         {"da_stages", &g_da_stages, 2, 3},

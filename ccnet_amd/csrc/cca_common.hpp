@@ -255,4 +255,31 @@ __device__ __forceinline__ void barrier_dma_keep_n(int n) {
     }
 }
 
+// Traversal order of a streaming launch (option "cache_order", cca_api.hip): a launch that walks its strips image by
+// image leaves the LAST images it touched in the 256 MiB Infinity Cache, so the launch that re-reads them next should
+// START there.  order 0: strip id as decoded; order 1: the strips in reverse logical order.  Applied AFTER the tail
+// split and the XCD decode (xcd_logical_id above and its relatives) have produced a strip id and a channel range, so
+// whole strips still come first in dispatch order and the cut ones last, with their channel ranges.  Placement and
+// order only affect speed, never results.  (Kept at the end of this header: tests/test_emu_modes.py names the lines
+// of barrier_dma_keep_n.)
+__device__ __forceinline__ int strip_in_order(int id, int strips, int order) { return order ? strips - 1 - id : id; }
+
+// Image-major, XCD-contiguous strip decode for launches whose strips are the G rows of B images, B % 8 == 0 (the host
+// checks it): inside an image, run s of 8 takes the rows [s G / 8, (s + 1) G / 8) -- 12 or 13 of 97 -- and sits on XCD
+// (s + image) % 8, so that over 8 consecutive images every XCD receives each run once: G strips per 8 images, B G / 8
+// in all, and every XCD is in the same image at the same time.  Returns the strip id of position p, 0 <= p < B G / 8,
+// in XCD x's list (images ascending, rows ascending inside a run).  Neighbouring rows share an L2 except at the seven
+// run boundaries of an image.
+__device__ __forceinline__ int xcd_image_major_strip(int x, int p, int G) {
+    const int grp = p / G;
+    int r = p - grp * G, b = 8 * grp, g = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int s = (x - j) & 7, lo = (s * G) >> 3, len = (((s + 1) * G) >> 3) - lo;
+        if (r >= 0 && r < len) { b += j; g = lo + r; r = -1; }        // (found: r stays negative from here on)
+        else r -= len;
+    }
+    return b * G + g;
+}
+
 }  // namespace cca

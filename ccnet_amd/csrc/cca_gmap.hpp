@@ -203,6 +203,10 @@ struct GmapJob {
     int red_n;
     float *red_dst;
     int xcd;          // > 0: strips per XCD of the XCD-aware strip decode (non-DUAL launches; see the kernel)
+    // traversal order (non-DUAL launches, option "cache_order"): bit 0 = the strips in reverse logical order (strip_in_order,
+    // cca_common.hpp), bit 1 = with xcd > 0, the image-major XCD decode (xcd_image_major_strip) instead of "XCD x = strips
+    // [x xcd, (x + 1) xcd)".  0 = the decode as it always was.
+    int order;
     // P3 (three-plane output, see the kernel): elements between the planes of a pixel's row, the column-sum partials of job 0
     // (``cs``: row stride ``cs_stride`` floats, pre-offset to the job's first channel) and of job 1 (DUAL)
     int p3_plane;
@@ -295,20 +299,27 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
         // rows share their boundary cache lines (a row of 97 floats is 388 B at arbitrary alignment): on one XCD the second
         // touch of such a line is an L2 hit and the two partial writes merge there (forward row pass 155 -> 148 us, same run:
         // profiles/r04m_ab_*.txt).
+        // Order bit 1 (the host offers it when the images divide by 8 as well): the XCD's list is image-major instead -- all
+        // eight XCDs work on ONE image at a time, each on a contiguous run of its rows -- so that the launch has an image order
+        // at all (with one image per XCD every image is live from the first workgroup to the last).
         const int x = id & 7, idx = id >> 3, nw8 = n_whole >> 3;
-        if (idx < nw8) {
-            id = x * j1.xcd + idx;
-        } else {
+        int pos = idx;                                                  // position in the XCD's list of strips
+        if (idx >= nw8) {
             const int r = idx - nw8, part = r % split;
-            id = x * j1.xcd + nw8 + r / split;
+            pos = nw8 + r / split;
             cg0 = part * ncg / split;
             cg1 = (part + 1) * ncg / split;
         }
-    } else if (id >= n_whole) {
-        const int r = id - n_whole, part = r % split;
-        id = n_whole + r / split;
-        cg0 = part * ncg / split;
-        cg1 = (part + 1) * ncg / split;
+        id = (j1.order & 2) ? xcd_image_major_strip(x, pos, G) : x * j1.xcd + pos;
+        id = strip_in_order(id, 8 * j1.xcd, j1.order & 1);
+    } else {
+        if (id >= n_whole) {
+            const int r = id - n_whole, part = r % split;
+            id = n_whole + r / split;
+            cg0 = part * ncg / split;
+            cg1 = (part + 1) * ncg / split;
+        }
+        if (!DUAL) id = strip_in_order(id, n_whole + ((int)gridDim.x - n_whole) / split, j1.order & 1);
     }
     const int id0 = id;                         // (the strip: the row of the P3 column-sum partials)
     // LONG: id = (strip, query block); this launch contracts over key block j1.jblk
@@ -705,11 +716,12 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
 // (functions.py:46-47 under bf16: out_H and out_W are each a bf16 bmm result before they are added) -- half the bytes of the
 // fp32 partial, which at BASELINE configs[4] was 2.2 GB of the step's 8.85 GB.  Two N tiles of a position are paired through one
 // lane exchange (lane ^ 16) so that a lane still stores 16 bytes: 8 consecutive bf16 channels.
+// ``order`` (option "cache_order"): 1 = the strips in reverse logical order (strip_in_order, cca_common.hpp), 0 = as dispatched.
 template <int P, bool ROW, bool TRANS, bool ADD, int NBUF = 3, int WPC = 2, typename FT = bf16p_t, typename OT = float>
 __global__ __launch_bounds__(GS_THREADS, WPC) void gmap3_kernel(const float *__restrict__ T, const FT *__restrict__ F,
                                                                const float *__restrict__ addend, const float *__restrict__ gamma,
                                                                OT *__restrict__ out, int C, int H, int W, long fbs, int fps,
-                                                               long abs_, int aps, long obs, int ops, int n_whole, int split) {
+                                                               long abs_, int aps, long obs, int ops, int n_whole, int split, int order) {
     constexpr bool OBF = std::is_same<OT, bf16_t>::value;
     static_assert(!OBF || (std::is_same<FT, bf16_t>::value && !ADD), "gmap3: the bf16 partial belongs to the bf16 family's column passes");
     constexpr int NT = (P + 15) / 16, TPW = (NT + GS_WAVES - 1) / GS_WAVES, NKS = P / 32;
@@ -735,6 +747,7 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap3_kernel(const float *__r
         cg0 = part * ncg / split;
         cg1 = (part + 1) * ncg / split;
     }
+    id = strip_in_order(id, n_whole + ((int)gridDim.x - n_whole) / split, order);      // (option "cache_order")
     const int b = id / G, g = id - b * G;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = uniform(tid >> 6);
     const int ln = lane & 15, lg = lane >> 4;
@@ -1378,10 +1391,12 @@ __global__ __launch_bounds__(GM_THREADS, SINGLE ? 2 : 1) void gweight_kernel(con
 // stays planes: it has to be transposed out of NCHW anyway.
 // NB: ring stages (0 = as many as fit the LDS: three at P = 100).  NB = 2 leaves 53 KB of the CU's LDS free: a column-pass workgroup
 // of the dv launch (gmap3_kernel<..., 2, 3>: 53,248 B) then runs NEXT TO the persistent workgroup instead of waiting for it to exit.
+// ``order`` (option "cache_order"): 1 = every workgroup walks ITS strips from the last image down (the ring runs on as before:
+// the stage sequence only names other strips), 0 = from the first image up.
 template <int P, typename FT = bf16p_t, typename YT = FT, int NB = 0>
 __global__ __launch_bounds__(GM_THREADS, 4) void gweight_stream_kernel(const FT *__restrict__ X, const YT *__restrict__ Y,
                                                                         float *__restrict__ T, int Cx, int B, int H, int W,
-                                                                        long xbs, int xps, long ybs, int yps) {
+                                                                        long xbs, int xps, long ybs, int yps, int order) {
     constexpr int NPL = std::is_same<FT, bf16p_t>::value ? 2 : 1;        // planes per operand
     static_assert(NPL == 2 || std::is_same<FT, bf16_t>::value, "gweight_stream: bf16p_t or bf16_t operands");
     constexpr int TSB = t16_size(P), NPB = t16_pieces(P);                 // one plane tile: dwords, 1 KiB pieces
@@ -1403,7 +1418,7 @@ __global__ __launch_bounds__(GM_THREADS, 4) void gweight_stream_kernel(const FT 
 
     struct Strip { int b, L, pix0, pstep, a_off; };
     auto strip_of = [&](int n) {                                            // the strip stage n belongs to
-        const int sidx = first + (n / nch) * step;
+        const int sidx = strip_in_order(first + (n / nch) * step, nstrips, order);      // (option "cache_order": images descending)
         const int b = sidx / S, r = sidx - b * S;
         const bool row = r >= W;
         const int g = row ? r - W : r;

@@ -384,6 +384,13 @@ int ccnet_cca_backward_planes3_f32(const float *dy, const float *q, const float 
  *                    measured best per family (2 on split planes, 1 on the bf16 / fp32 pixel-major entries).
  *   "planes_xcd"   1 (default): the NCHW row pass of the split-plane forward decodes its strips XCD-aware (consecutive rows of an
  *                    image on one XCD, whose L2 then merges the boundary lines neighbouring NCHW rows share); 0: linear.
+ *   "cache_order"  the order in which the streaming launches of the split-plane step (strips <= 100) walk the images, so that a launch
+ *                    starts on what its producer touched last and the 256 MiB Infinity Cache still holds.  A bit mask, a set bit =
+ *                    descending: 1 forward column pass, 2 forward NCHW row pass, 4 dA, 8 dv column pass, 16 dv row pass; 32 = the
+ *                    forward NCHW row pass decodes image-major over the XCDs with ascending images (bit 2 selects the same decode,
+ *                    descending; it needs what "planes_xcd" needs and B % 8 == 0, else today's decode runs, reversed if asked).
+ *                    0 = the traversal as it always was; -1 (default) = the shipped pattern.  Only moves workgroups: same bits.
+ *                    Read at launch time: a captured graph keeps the value it was captured with.
  *   "da_stages"    2 (default) / 3: LDS ring stages of the persistent dA kernel of the plane-free backward.  Three fill the CU's LDS,
  *                    so the dv column pass on the side stream waits for its workgroups to exit; two leave room for one column
  *                    workgroup per CU and the launches overlap for real (backward 0.45 -> 0.40 ms at the headline shape).

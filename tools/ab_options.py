@@ -2,7 +2,10 @@
 """A/B of library options on the headline split-plane step, on ONE set of buffers inside ONE process (boxes of the pool differ
 by 3-4 %, so only same-run comparisons count).  Per option set: eager step ms, hipGraph replay ms, fwd / bwd ms and -- with
 every launch on one stream -- the per-launch durations.
-usage: ab_options.py [B C H W] [--sets name=opt:val,opt:val ...]"""
+The "order-*" sets are the A/B of option "cache_order" (which streaming launches walk the images in descending order):
+a mask WINS only if its graph-replay step is below order-0's in EVERY round and its mean gain exceeds the largest difference
+between two rounds of one set -- the run's own noise; the closing table says so per set.
+usage: ab_options.py [B C H W] [--sets name,name,... ("order": every order-* set; "order-mNN": mask NN)] [--rounds N]"""
 import os
 import sys
 
@@ -12,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from ccnet_amd import _lib  # noqa: E402
 
-args = [a for i, a in enumerate(sys.argv[1:]) if not a.startswith("--") and sys.argv[i] != "--sets"]
+args = [a for i, a in enumerate(sys.argv[1:]) if not a.startswith("--") and sys.argv[i] not in ("--sets", "--rounds")]
 B, C, H, W = (int(a) for a in args[:4]) if len(args) >= 4 else (8, 512, 97, 97)
 DEFAULT_SETS = {
     "default": {},
@@ -26,18 +29,35 @@ DEFAULT_SETS = {
     "overlap-1": {"planes_overlap": 1},
     "dqdk-three-terms": {"dqdk_exact": 0},   # ca_backward with three bf16 terms per product instead of six (round 6 default: six, fp32-equivalent)
     "ring-2-per-cu": {"planes_ring": 1},     # the column ring passes with three slots and TWO workgroups per CU (slow-box A/B)
+    # "cache_order": bit 0 forward column pass (L3), 1 forward NCHW row pass (L4), 2 dA (L6), 3 dv column pass (L7), 4 dv row pass (L8)
+    # descending; bit 5 = L4 on the image-major XCD decode with ascending images
+    "order-0": {"cache_order": 0},                              # the traversal of before the option
+    "order-model": {"cache_order": 14},                         # L4, L6, L7 descending: the residency model's pattern
+    "order-L3": {"cache_order": 1},
+    "order-L4": {"cache_order": 2},
+    "order-L6": {"cache_order": 4},
+    "order-L7": {"cache_order": 8},
+    "order-L8": {"cache_order": 16},
+    "order-L4-xcd": {"cache_order": 32},
+    "order-model-no-xcd": {"cache_order": 14, "planes_xcd": 0},
+    "order-complement": {"cache_order": 17},                    # L3 and L8 descending, L4, L6, L7 ascending
 }
 if "--sets" in sys.argv:
     keep = sys.argv[sys.argv.index("--sets") + 1].split(",")
-    DEFAULT_SETS = {k: v for k, v in DEFAULT_SETS.items() if k in keep or k == "default"}
-DETAIL = ("one-stream", "dqdk-three-terms")
+    for k in keep:                                      # "order-mNN": any other mask of "cache_order"
+        if k.startswith("order-m") and k[7:].isdigit():
+            DEFAULT_SETS[k] = {"cache_order": int(k[7:])}
+    DEFAULT_SETS = {k: v for k, v in DEFAULT_SETS.items() if k in keep or k == "default" or ("order" in keep and k.startswith("order-"))}
+ROUNDS = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 2
+DETAIL = ("one-stream", "dqdk-three-terms") + tuple(k for k in DEFAULT_SETS if k.startswith("order-"))
 lib = _lib.get_lib()
 dev = torch.device("cuda:0")
 BASE = {"planes_ring": 2, "planes_stream": 1, "planes_overlap": -1, "planes_xcd": 1, "energy_tail": 1, "da_stages": 2, "dqdk_wpc3": 1,
-        "dqdk_exact": 1}
+        "dqdk_exact": 1, "cache_order": -1}
 wl = bench.PlanesWorkload(lib, B, C, H, W, dev, 1234)
 ref = None
-for rnd in range(2):                       # two rounds: the order of the sets must not matter
+graph_ms = {}                              # set -> graph-replay ms per round
+for rnd in range(ROUNDS):                  # (two rounds by default: the order of the sets must not matter)
     for name, opts in DEFAULT_SETS.items():
         for k, v in {**BASE, **opts}.items():
             if not k.startswith("_"):
@@ -58,6 +78,7 @@ for rnd in range(2):                       # two rounds: the order of the sets m
         g.replay()
         gms = bench.time_region(g.replay, 50)
         del g
+        graph_ms.setdefault(name, []).append(gms)
         print(f"== round {rnd} {name:16s} {opts}: eager {ms:.4f} ms  graph {gms:.4f} ms  fwd {fwd:.4f}  bwd {bwd:.4f}  bit-identical to first: {same}", flush=True)
         if rnd == 0 and name in DETAIL:
             lib.set_option("planes_overlap", 0)          # per-launch durations: every launch on one stream
@@ -69,3 +90,11 @@ for rnd in range(2):                       # two rounds: the order of the sets m
             lib.set_option("planes_overlap", -1)
 for k, v in BASE.items():
     lib.set_option(k, v)
+if "order-0" in graph_ms:
+    base = graph_ms["order-0"]
+    print("== cache_order: graph-replay ms per round; noise = the larger of the set's and order-0's spread over the rounds")
+    for name, v in graph_ms.items():
+        gain, noise = sum(base) / len(base) - sum(v) / len(v), max(max(v) - min(v), max(base) - min(base))
+        below = all(a < b for a, b in zip(v, base))
+        print(f"   {name:20s} " + " ".join(f"{x:.4f}" for x in v) + f"  mean {sum(v) / len(v):.4f}  gain over order-0 {gain * 1e3:+6.1f} us  noise {noise * 1e3:4.1f} us"
+              f"  below order-0 in every round: {below}  wins: {name != 'order-0' and below and gain > noise}")
