@@ -9,13 +9,14 @@ from .abn import ABN, InPlaceABN, InPlaceABNSync, convert_abn
 from .dsn import UpsampledCrossEntropy2d, UpsampledCrossEntropyFunction
 from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFunction, INF, ca_map, ca_softmax,
                         ca_weight, criss_cross_attention, graph_module)
-from .evaluate import SegEvaluator, predict_sliding, predict_whole
+from .evaluate import MultiScaleEvaluator, SegEvaluator, predict_multiscale, predict_sliding, predict_whole, scaled_size
 from .lovasz import CriterionOhemDSN2, LovaszSoftmax, LovaszSoftmaxFunction, lovasz_softmax
 from .ohem import CriterionOhemDSN, OhemCrossEntropy2d
 
 __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "ca_weight", "ca_map",
            "ca_softmax", "criss_cross_attention", "graph_module", "INF", "OhemCrossEntropy2d", "CriterionOhemDSN",
-           "SegEvaluator", "predict_sliding", "predict_whole", "lovasz_softmax", "LovaszSoftmax", "LovaszSoftmaxFunction",
+           "SegEvaluator", "predict_sliding", "predict_whole", "MultiScaleEvaluator", "predict_multiscale", "scaled_size",
+           "lovasz_softmax", "LovaszSoftmax", "LovaszSoftmaxFunction",
            "CriterionOhemDSN2", "ABN", "InPlaceABN", "InPlaceABNSync", "convert_abn", "UpsampledCrossEntropy2d",
            "UpsampledCrossEntropyFunction"]
 __version__ = "0.1.0"

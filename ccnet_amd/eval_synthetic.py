@@ -5,6 +5,9 @@
     data       image i: randn(1, 3, H, W), labels randint(0, C) with ~5 % set to 255, from a generator seeded with seed + i
     inference  SegEvaluator: the 8 zero-padded 769^2 tiles of a 1024 x 2048 image (--whole: the image itself), --flip adds
                the mirrored image's tiles; one net call per image, one HIP kernel for the score, argmax and confusion
+    scales     --scales 0.75,1.0,1.25 evaluates every image at those scales (MultiScaleEvaluator, include/ccnet_mseval.h):
+               per scale a gather kernel zooms, mirrors and cuts the tiles, the net runs over --tile-batch tiles at a time, and
+               one kernel resamples the scale's score back and accumulates; the default 1.0 is the single-scale path above
     parallel   under torch.distributed.run rank r takes images r, r + world, ...; result() sums the confusion counts
 
 Launch:   python -m ccnet_amd.eval_synthetic --images 8
@@ -34,8 +37,16 @@ def synthetic_image(i, H, W, num_classes, seed, device):
     return image, label.masked_fill(ignore, 255)
 
 
+def parse_scales(text):
+    """"0.75,1.0,1.25" -> (0.75, 1.0, 1.25)."""
+    scales = tuple(float(v) for v in str(text).split(",") if v.strip())
+    if not scales or min(scales) <= 0:
+        raise SystemExit(f"--scales {text!r}: a comma-separated list of positive numbers")
+    return scales
+
+
 def run(args, quiet=False):
-    from .evaluate import SegEvaluator, all_reduce_confusion, mean_iou, shard_indices
+    from .evaluate import MultiScaleEvaluator, SegEvaluator, all_reduce_confusion, mean_iou, shard_indices
     from .segmodel import Seg_Model, load_model
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -59,7 +70,12 @@ def run(args, quiet=False):
         torch.cuda.reset_peak_memory_stats(device)
     routes = set()
     model.head.cca.register_forward_pre_hook(lambda m, inp: routes.add(m.route(inp[0])))
-    ev = SegEvaluator(args.num_classes, tile_size=(args.tile, args.tile), whole=args.whole, flip=args.flip, device=device)
+    scales = parse_scales(args.scales)
+    if scales == (1.0,):
+        ev = SegEvaluator(args.num_classes, tile_size=(args.tile, args.tile), whole=args.whole, flip=args.flip, device=device)
+    else:
+        ev = MultiScaleEvaluator(args.num_classes, scales=scales, tile_size=(args.tile, args.tile), whole=args.whole,
+                                 flip=args.flip, tile_batch=args.tile_batch, device=device)
 
     def net(x):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.bf16):
@@ -111,6 +127,9 @@ def run(args, quiet=False):
                        "weights": "restored" if args.restore_from else "random"},
             "counted_pixels": int(counts.sum()),
         }
+        if scales != (1.0,):
+            result["config"].update(scales=list(scales), tile_batch=args.tile_batch,
+                                    tiles=[len(g[2]) for g in ev.geometry(args.height, args.width)])
         if args.abn is not None:
             result["abn"] = args.abn
             result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
@@ -131,6 +150,8 @@ def build_parser():
     ap.add_argument("--tile", type=int, default=769, help="square tile of the sliding window (evaluate.py: 769)")
     ap.add_argument("--whole", action="store_true", help="one tile equal to the image (evaluate.py --whole)")
     ap.add_argument("--flip", action="store_true", help="average with the horizontally mirrored image's prediction")
+    ap.add_argument("--scales", type=str, default="1.0", help="comma-separated scales, e.g. 0.75,1.0,1.25 (multi-scale evaluation)")
+    ap.add_argument("--tile-batch", type=int, default=8, help="multi-scale: tiles per net call")
     ap.add_argument("--recurrence", type=int, default=2)
     ap.add_argument("--num-classes", type=int, default=19)
     ap.add_argument("--bf16", action="store_true", help="run the net under bf16 autocast (the kernel reads its output as fp32)")
