@@ -12,11 +12,12 @@ from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFuncti
 from .evaluate import MultiScaleEvaluator, SegEvaluator, predict_multiscale, predict_sliding, predict_whole, scaled_size
 from .lovasz import CriterionOhemDSN2, LovaszSoftmax, LovaszSoftmaxFunction, lovasz_softmax
 from .ohem import CriterionOhemDSN, OhemCrossEntropy2d
+from .ohemdsn import UpsampledOhemCrossEntropy2d, UpsampledOhemFunction
 
 __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "ca_weight", "ca_map",
            "ca_softmax", "criss_cross_attention", "graph_module", "INF", "OhemCrossEntropy2d", "CriterionOhemDSN",
            "SegEvaluator", "predict_sliding", "predict_whole", "MultiScaleEvaluator", "predict_multiscale", "scaled_size",
            "lovasz_softmax", "LovaszSoftmax", "LovaszSoftmaxFunction",
            "CriterionOhemDSN2", "ABN", "InPlaceABN", "InPlaceABNSync", "convert_abn", "UpsampledCrossEntropy2d",
-           "UpsampledCrossEntropyFunction"]
+           "UpsampledCrossEntropyFunction", "UpsampledOhemCrossEntropy2d", "UpsampledOhemFunction"]
 __version__ = "0.1.0"

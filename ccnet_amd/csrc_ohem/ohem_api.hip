@@ -11,9 +11,8 @@
 
 namespace {
 
-// scipy.ndimage.zoom's output length round(n * (1 / factor)) (ties to even) and its grid_mode=False source step
-int zoom_len(int n, int factor) { return (int)nearbyint(n * (1.0 / factor)); }
-double zoom_step(int n, int n_out) { return n_out > 1 ? (double)(n - 1) / (double)(n_out - 1) : 1.0; }
+using ohem::zoom_len;      // (scipy.ndimage.zoom's output length and source step: ohem_kernels.hpp)
+using ohem::zoom_step;
 
 struct Layout {
     int N, ho, wo, M, nblk;

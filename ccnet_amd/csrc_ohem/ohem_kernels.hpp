@@ -73,19 +73,20 @@ __device__ __forceinline__ float target_prob(const float *logits, int C, int H, 
     return expf(px[(size_t)t * plane] - m) / s;
 }
 
-__global__ __launch_bounds__(kPixThreads) void zoom_keys_kernel(const float *logits, const int64_t *labels, uint32_t *keys,
-                                                                int B, int C, int H, int W, int ho, int wo, double zy,
-                                                                double zx, long long ignore) {
-    const int i = blockIdx.x * kPixThreads + threadIdx.x;
-    if (i >= B * ho * wo) return;
-    const int b = i / (ho * wo), r = i - b * (ho * wo), oy = r / wo, ox = r - oy * wo;
+// scipy.ndimage.zoom's output length round(n * (1 / factor)) (ties to even) and its grid_mode=False source step (host side)
+inline int zoom_len(int n, int factor) { return (int)nearbyint(n * (1.0 / factor)); }
+inline double zoom_step(int n, int n_out) { return n_out > 1 ? (double)(n - 1) / (double)(n_out - 1) : 1.0; }
+
+// the key of zoomed pixel (oy, ox) of image b: scipy's order-0 pick of the label, the four taps of its order-1 zoom, double
+// weights in scipy's tap order.  `prob(t, y, x)` is the fp32 probability of class t at full-resolution pixel (y, x) of that
+// image; where that comes from is the caller's (a softmax of stored logits here, of interpolated ones in ohemdsn_kernels.hpp).
+template <class Prob>
+__device__ __forceinline__ uint32_t zoom_key(const int64_t *labels, int b, int C, int H, int W, int oy, int ox, double zy,
+                                             double zx, long long ignore, Prob prob) {
     const double cy = oy * zy, cx = ox * zx;
     const int ly = imin((int)floor(cy + 0.5), H - 1), lx = imin((int)floor(cx + 0.5), W - 1);
     const long long lab = labels[(size_t)b * H * W + (size_t)ly * W + lx];
-    if (lab == ignore || lab < 0 || lab >= C) {
-        keys[i] = kInvalidKey;
-        return;
-    }
+    if (lab == ignore || lab < 0 || lab >= C) return kInvalidKey;
     const int t = (int)lab;
     const int y0 = (int)floor(cy), x0 = (int)floor(cx);
     const int y1 = imin(y0 + 1, H - 1), x1 = imin(x0 + 1, W - 1);
@@ -94,8 +95,18 @@ __global__ __launch_bounds__(kPixThreads) void zoom_keys_kernel(const float *log
     const int ys[2] = {y0, y1}, xs[2] = {x0, x1};
     double acc = 0.0;
     for (int a = 0; a < 2; ++a)
-        for (int e = 0; e < 2; ++e) acc += (double)target_prob(logits, C, H, W, b, t, ys[a], xs[e]) * wy[a] * wx[e];
-    keys[i] = float_to_bits((float)acc);
+        for (int e = 0; e < 2; ++e) acc += (double)prob(t, ys[a], xs[e]) * wy[a] * wx[e];
+    return float_to_bits((float)acc);
+}
+
+__global__ __launch_bounds__(kPixThreads) void zoom_keys_kernel(const float *logits, const int64_t *labels, uint32_t *keys,
+                                                                int B, int C, int H, int W, int ho, int wo, double zy,
+                                                                double zx, long long ignore) {
+    const int i = blockIdx.x * kPixThreads + threadIdx.x;
+    if (i >= B * ho * wo) return;
+    const int b = i / (ho * wo), r = i - b * (ho * wo), oy = r / wo, ox = r - oy * wo;
+    keys[i] = zoom_key(labels, b, C, H, W, oy, ox, zy, zx, ignore,
+                       [&](int t, int y, int x) { return target_prob(logits, C, H, W, b, t, y, x); });
 }
 
 __global__ __launch_bounds__(kSelectThreads) void select_kernel(const uint32_t *keys, int M, int min_kept_zoomed, float thresh,

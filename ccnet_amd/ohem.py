@@ -93,7 +93,8 @@ class CriterionOhemDSN(nn.Module):
     """OHEM cross-entropy on the up-sampled main logits + 0.4 x cross-entropy on the up-sampled DSN logits
     (loss/criterion.py:37-56).  The bilinear up-sampling stays a stock op, as in the reference; with ``fused_aux=True`` the
     second, plain cross-entropy head runs on :class:`ccnet_amd.dsn.UpsampledCrossEntropy2d` instead, which up-samples
-    inside its kernels (the OHEM head needs the full-resolution map for its threshold search and keeps the stock op)."""
+    inside its kernels (the OHEM head keeps the stock op here).  :class:`ccnet_amd.ohemdsn.CriterionOhemDSN` is the fully fused
+    form: both heads, the threshold search included, on kernels that up-sample as they read."""
 
     def __init__(self, ignore_index=255, thresh=0.7, min_kept=100000, use_weight=True, reduction="mean", fused_aux=False):
         super().__init__()

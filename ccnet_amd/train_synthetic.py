@@ -9,6 +9,8 @@ the same training step on random data, one process per GPU:
                --lovasz: CriterionOhemDSN2 (CE + Lovász-softmax, DSN head unused)   loss/criterion.py:59-78
                --fused-dsn: ccnet_amd.dsn.CriterionDSN (the up-sample inside the loss kernels); with --ohem,
                CriterionOhemDSN(fused_aux=True); refused with --lovasz
+               --fused-ohem: ccnet_amd.ohemdsn.CriterionOhemDSN (implies --ohem: the OHEM head up-samples inside its kernels
+               too); refused with --lovasz and with --fused-dsn
                --abn device|inplace: every inplace_abn layer swapped for its HIP twin (ccnet_amd.abn.convert_abn)
     data       images randn(b,3,769,769), labels randint(0,19) with ~5 % set to 255 train.py:28-33 (crop 769)
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
@@ -71,6 +73,9 @@ def run(args, model_factory=None, quiet=False):
         fused_dsn = getattr(args, "fused_dsn", False)
         if getattr(args, "lovasz", False):
             criterion = CriterionOhemDSN2()
+        elif getattr(args, "fused_ohem", False):
+            from .ohemdsn import CriterionOhemDSN as FusedCriterionOhemDSN
+            criterion = FusedCriterionOhemDSN(thresh=args.ohem_thres, min_kept=args.ohem_keep)
         elif getattr(args, "ohem", False):
             criterion = CriterionOhemDSN(thresh=args.ohem_thres, min_kept=args.ohem_keep, fused_aux=fused_dsn)
         elif fused_dsn:
@@ -86,7 +91,7 @@ def run(args, model_factory=None, quiet=False):
         from .abn import convert_abn
         convert_abn(model, abn_mode)
     model = model.to(device).train()
-    if use_cuda and (abn_mode is not None or getattr(args, "fused_dsn", False)):
+    if use_cuda and (abn_mode is not None or getattr(args, "fused_dsn", False) or getattr(args, "fused_ohem", False)):
         torch.cuda.reset_peak_memory_stats(device)
     net = model
     if ddp:
@@ -155,6 +160,10 @@ def run(args, model_factory=None, quiet=False):
             result["criterion"] = "ohem+dsn-fused" if getattr(args, "ohem", False) else "dsn-fused"
             if use_cuda:
                 result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
+        if getattr(args, "fused_ohem", False):
+            result["criterion"] = "ohem-fused"
+            if use_cuda:
+                result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
         if abn_mode is not None:
             result["abn"] = abn_mode
             result["step_losses"] = [round(float(v.float().item()), 6) for v in losses]
@@ -193,6 +202,11 @@ def build_parser():
                          "with --ohem the DSN head of CriterionOhemDSN (fused_aux=True); refused with --lovasz, whose criterion "
                          "needs the full-resolution map; the JSON line then reports criterion dsn-fused (ohem+dsn-fused) and "
                          "max_memory_allocated_mb")
+    ap.add_argument("--fused-ohem", action="store_true",
+                    help="the whole --ohem criterion on kernels that up-sample as they read (ccnet_amd.ohemdsn.CriterionOhemDSN: "
+                         "threshold search, keep decision and both heads' gradients from the low-resolution logits); implies "
+                         "--ohem; refused with --lovasz and with --fused-dsn; the JSON line then reports criterion ohem-fused "
+                         "and max_memory_allocated_mb")
     ap.add_argument("--abn", choices=("torch", "device", "inplace"), default=None,
                     help="normalisation layers: torch (the default: the stock inplace_abn restatement), device (the HIP ABN "
                          "kernels, out of place, relu and residual adds fused in the residual units) or inplace (HIP ABN "
@@ -212,6 +226,12 @@ def check_args(args):
     if getattr(args, "fused_dsn", False) and getattr(args, "lovasz", False):
         raise ValueError("--fused-dsn cannot be combined with --lovasz: CriterionOhemDSN2 takes the Lovász-softmax of the "
                          "full-resolution map and leaves the DSN head unused")
+    if getattr(args, "fused_ohem", False) and getattr(args, "lovasz", False):
+        raise ValueError("--fused-ohem cannot be combined with --lovasz: it selects the OHEM criterion, CriterionOhemDSN2 is "
+                         "another one")
+    if getattr(args, "fused_ohem", False) and getattr(args, "fused_dsn", False):
+        raise ValueError("--fused-ohem cannot be combined with --fused-dsn: it already up-samples both heads inside its kernels "
+                         "(--ohem --fused-dsn keeps the stock up-sample of the OHEM head)")
 
 
 def parse_args(argv=None):
@@ -222,6 +242,8 @@ def parse_args(argv=None):
         check_args(args)
     except ValueError as e:
         ap.error(str(e))
+    if args.fused_ohem:
+        args.ohem = True                                      # (--fused-ohem implies --ohem)
     return args
 
 
