@@ -5,7 +5,9 @@ ctypes binding (:mod:`ccnet_amd._lib`) and the host-side mirror of the reference
 ``cc_attention/functions.py`` (:mod:`ccnet_amd.functions`).  Importing the package does not load the
 device library; the first kernel call does, and fails loudly if it has not been built.
 """
+from . import celovasz
 from .abn import ABN, InPlaceABN, InPlaceABNSync, convert_abn
+from .celovasz import UpsampledCELovasz, UpsampledCELovaszFunction
 from .dsn import UpsampledCrossEntropy2d, UpsampledCrossEntropyFunction
 from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFunction, INF, ca_map, ca_softmax,
                         ca_weight, criss_cross_attention, graph_module)
@@ -19,5 +21,6 @@ __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "
            "SegEvaluator", "predict_sliding", "predict_whole", "MultiScaleEvaluator", "predict_multiscale", "scaled_size",
            "lovasz_softmax", "LovaszSoftmax", "LovaszSoftmaxFunction",
            "CriterionOhemDSN2", "ABN", "InPlaceABN", "InPlaceABNSync", "convert_abn", "UpsampledCrossEntropy2d",
-           "UpsampledCrossEntropyFunction", "UpsampledOhemCrossEntropy2d", "UpsampledOhemFunction"]
+           "UpsampledCrossEntropyFunction", "UpsampledOhemCrossEntropy2d", "UpsampledOhemFunction",
+           "celovasz", "UpsampledCELovasz", "UpsampledCELovaszFunction"]
 __version__ = "0.1.0"

@@ -11,6 +11,8 @@ the same training step on random data, one process per GPU:
                CriterionOhemDSN(fused_aux=True); refused with --lovasz
                --fused-ohem: ccnet_amd.ohemdsn.CriterionOhemDSN (implies --ohem: the OHEM head up-samples inside its kernels
                too); refused with --lovasz and with --fused-dsn
+               --fused-lovasz: ccnet_amd.celovasz.CriterionOhemDSN2 (implies --lovasz: the up-sample, the softmax and the
+               cross-entropy inside the Lovász criterion's kernels); refused with --ohem, --fused-dsn and --fused-ohem
                --abn device|inplace: every inplace_abn layer swapped for its HIP twin (ccnet_amd.abn.convert_abn)
     data       images randn(b,3,769,769), labels randint(0,19) with ~5 % set to 255 train.py:28-33 (crop 769)
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
@@ -71,7 +73,10 @@ def run(args, model_factory=None, quiet=False):
     if model_factory is None:
         from .segmodel import CriterionDSN, CriterionOhemDSN, CriterionOhemDSN2, Seg_Model
         fused_dsn = getattr(args, "fused_dsn", False)
-        if getattr(args, "lovasz", False):
+        if getattr(args, "fused_lovasz", False):
+            from .celovasz import CriterionOhemDSN2 as FusedCriterionOhemDSN2
+            criterion = FusedCriterionOhemDSN2()
+        elif getattr(args, "lovasz", False):
             criterion = CriterionOhemDSN2()
         elif getattr(args, "fused_ohem", False):
             from .ohemdsn import CriterionOhemDSN as FusedCriterionOhemDSN
@@ -91,12 +96,14 @@ def run(args, model_factory=None, quiet=False):
         from .abn import convert_abn
         convert_abn(model, abn_mode)
     model = model.to(device).train()
-    if use_cuda and (abn_mode is not None or getattr(args, "fused_dsn", False) or getattr(args, "fused_ohem", False)):
+    if use_cuda and (abn_mode is not None or getattr(args, "fused_dsn", False) or getattr(args, "fused_ohem", False)
+                     or getattr(args, "fused_lovasz", False)):
         torch.cuda.reset_peak_memory_stats(device)
     net = model
     if ddp:
         # CriterionOhemDSN2 leaves the DSN head's output unused: DDP must not wait for its gradients
-        extra = {"find_unused_parameters": True} if getattr(args, "lovasz", False) else {}
+        lovasz = getattr(args, "lovasz", False) or getattr(args, "fused_lovasz", False)
+        extra = {"find_unused_parameters": True} if lovasz else {}
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if use_cuda else None,
                                                         broadcast_buffers=False, **extra)
     opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.weight_decay)
@@ -164,6 +171,10 @@ def run(args, model_factory=None, quiet=False):
             result["criterion"] = "ohem-fused"
             if use_cuda:
                 result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
+        if getattr(args, "fused_lovasz", False):
+            result["criterion"] = "lovasz-fused"
+            if use_cuda:
+                result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
         if abn_mode is not None:
             result["abn"] = abn_mode
             result["step_losses"] = [round(float(v.float().item()), 6) for v in losses]
@@ -207,6 +218,11 @@ def build_parser():
                          "threshold search, keep decision and both heads' gradients from the low-resolution logits); implies "
                          "--ohem; refused with --lovasz and with --fused-dsn; the JSON line then reports criterion ohem-fused "
                          "and max_memory_allocated_mb")
+    ap.add_argument("--fused-lovasz", action="store_true",
+                    help="the whole --lovasz criterion on kernels that up-sample and soft-max as they read "
+                         "(ccnet_amd.celovasz.CriterionOhemDSN2: the Lovász errors, the cross-entropy and the gradient from the "
+                         "low-resolution logits); implies --lovasz; refused with --ohem, --fused-dsn and --fused-ohem; the JSON "
+                         "line then reports criterion lovasz-fused and max_memory_allocated_mb")
     ap.add_argument("--abn", choices=("torch", "device", "inplace"), default=None,
                     help="normalisation layers: torch (the default: the stock inplace_abn restatement), device (the HIP ABN "
                          "kernels, out of place, relu and residual adds fused in the residual units) or inplace (HIP ABN "
@@ -232,6 +248,16 @@ def check_args(args):
     if getattr(args, "fused_ohem", False) and getattr(args, "fused_dsn", False):
         raise ValueError("--fused-ohem cannot be combined with --fused-dsn: it already up-samples both heads inside its kernels "
                          "(--ohem --fused-dsn keeps the stock up-sample of the OHEM head)")
+    if getattr(args, "fused_lovasz", False):
+        if getattr(args, "fused_ohem", False):
+            raise ValueError("--fused-lovasz cannot be combined with --fused-ohem: it selects CriterionOhemDSN2, the OHEM "
+                             "criterion is another one")
+        if getattr(args, "ohem", False):
+            raise ValueError("--fused-lovasz cannot be combined with --ohem: it selects CriterionOhemDSN2, which does no OHEM "
+                             "despite its name")
+        if getattr(args, "fused_dsn", False):
+            raise ValueError("--fused-lovasz cannot be combined with --fused-dsn: CriterionOhemDSN2 leaves the DSN head unused "
+                             "and already up-samples the main head inside its kernels")
 
 
 def parse_args(argv=None):
@@ -244,6 +270,8 @@ def parse_args(argv=None):
         ap.error(str(e))
     if args.fused_ohem:
         args.ohem = True                                      # (--fused-ohem implies --ohem)
+    if args.fused_lovasz:
+        args.lovasz = True                                    # (--fused-lovasz implies --lovasz)
     return args
 
 
