@@ -5,8 +5,10 @@ ctypes binding (:mod:`ccnet_amd._lib`) and the host-side mirror of the reference
 ``cc_attention/functions.py`` (:mod:`ccnet_amd.functions`).  Importing the package does not load the
 device library; the first kernel call does, and fails loudly if it has not been built.
 """
-from . import celovasz
+from . import augment, celovasz
 from .abn import ABN, InPlaceABN, InPlaceABNSync, convert_abn
+from .augment import (CITYSCAPES_ID_TO_TRAINID, AugmentParams, CSDataSet, DeviceAugment, DevicePrefetcher, VOCDataSet,
+                      draw_params)
 from .celovasz import UpsampledCELovasz, UpsampledCELovaszFunction
 from .dsn import UpsampledCrossEntropy2d, UpsampledCrossEntropyFunction
 from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFunction, INF, ca_map, ca_softmax,
@@ -22,5 +24,6 @@ __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "
            "lovasz_softmax", "LovaszSoftmax", "LovaszSoftmaxFunction",
            "CriterionOhemDSN2", "ABN", "InPlaceABN", "InPlaceABNSync", "convert_abn", "UpsampledCrossEntropy2d",
            "UpsampledCrossEntropyFunction", "UpsampledOhemCrossEntropy2d", "UpsampledOhemFunction",
-           "celovasz", "UpsampledCELovasz", "UpsampledCELovaszFunction"]
+           "celovasz", "UpsampledCELovasz", "UpsampledCELovaszFunction", "augment", "DeviceAugment", "DevicePrefetcher",
+           "CSDataSet", "VOCDataSet", "AugmentParams", "draw_params", "CITYSCAPES_ID_TO_TRAINID"]
 __version__ = "0.1.0"

@@ -15,6 +15,9 @@ the same training step on random data, one process per GPU:
                cross-entropy inside the Lovász criterion's kernels); refused with --ohem, --fused-dsn and --fused-ohem
                --abn device|inplace: every inplace_abn layer swapped for its HIP twin (ccnet_amd.abn.convert_abn)
     data       images randn(b,3,769,769), labels randint(0,19) with ~5 % set to 255 train.py:28-33 (crop 769)
+               --device-augment: synthetic uint8 1024 x 2048 frames and Cityscapes id labels, made once; every step draws
+               the reference's scale, offsets and mirror and builds its batch with ccnet_amd.augment.DeviceAugment
+               (dataset/datasets.py:173-210 as one HIP gather); composes with every criterion flag
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
                per-rank seed = rank                                                  train.py:154-155
@@ -48,6 +51,40 @@ def synthetic_batch(batch, size, num_classes, device, generator):
     return images, labels.masked_fill(ignore, 255)
 
 
+class AugmentedSource:
+    """--device-augment: ``batch`` synthetic uint8 frames and id labels, packed on the device once; ``next()`` draws each
+    sample's parameters as the reference's dataset would (generators of its own, seeded per rank) and returns the batch that
+    DeviceAugment makes of them."""
+
+    def __init__(self, batch, frame, size, device, seed):
+        import random
+
+        import numpy as np
+
+        from . import augment
+        if device.type != "cuda":
+            raise RuntimeError("--device-augment needs a HIP device (ccnet_amd has no CPU fallback for the input-pipeline kernel)")
+        self.augment, self.crop, self.frame = augment, (size, size), tuple(frame)
+        self.rng, self.np_rng = random.Random(seed), np.random.RandomState(seed)
+        data = np.random.RandomState(seed)
+        h, w = self.frame
+        self.frames = [data.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(batch)]
+        self.labels = [data.randint(0, 34, (h, w)).astype(np.uint8) for _ in range(batch)]
+        frames, labels, _ = augment.pack(self.frames, self.labels, self.draw())
+        self.frames_dev, self.labels_dev = frames.to(device), labels.to(device)
+        self.run = augment.DeviceAugment(self.crop, (104.00698793, 116.66876762, 122.67891434), 255,
+                                         augment.CITYSCAPES_ID_TO_TRAINID, "rgb")       # train.py's IMG_MEAN
+
+    def draw(self):
+        h, w = self.frame
+        return [self.augment.draw_params(h, w, self.crop, rng=self.rng, np_rng=self.np_rng) for _ in self.frames]
+
+    def next(self):
+        # (only the descriptor table changes from step to step: the frames stay where they are)
+        desc = self.augment.descriptors([f.shape[:2] for f in self.frames], self.draw(), pin=True)
+        return self.run(self.frames_dev, self.labels_dev, desc)
+
+
 def run(args, model_factory=None, quiet=False):
     """One training job on the calling rank; returns the result dict (rank 0) or None.  ``quiet`` suppresses the
     JSON line (bench.py embeds the result in its own line)."""
@@ -69,6 +106,9 @@ def run(args, model_factory=None, quiet=False):
     if ddp and not dist.is_initialized():
         dist.init_process_group("nccl" if use_cuda else "gloo")
     torch.manual_seed(args.seed + rank)                       # per-rank seed (train.py:154-155)
+    source = None
+    if getattr(args, "device_augment", False):
+        source = AugmentedSource(args.batch_per_gpu, args.augment_frame, args.size, device, args.seed + rank)
 
     if model_factory is None:
         from .segmodel import CriterionDSN, CriterionOhemDSN, CriterionOhemDSN2, Seg_Model
@@ -114,7 +154,10 @@ def run(args, model_factory=None, quiet=False):
     def step(it):
         for g in opt.param_groups:
             g["lr"] = lr_poly(args.lr, it, max(total, 1))
-        images, labels = synthetic_batch(args.batch_per_gpu, args.size, args.num_classes, device, gen)
+        if source is not None:
+            images, labels = source.next()
+        else:
+            images, labels = synthetic_batch(args.batch_per_gpu, args.size, args.num_classes, device, gen)
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.bf16 and use_cuda):
             loss = net(images, labels)
@@ -175,6 +218,8 @@ def run(args, model_factory=None, quiet=False):
             result["criterion"] = "lovasz-fused"
             if use_cuda:
                 result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
+        if source is not None:
+            result["data"] = "synthetic uint8 %d x %d frames through DeviceAugment" % source.frame
         if abn_mode is not None:
             result["abn"] = abn_mode
             result["step_losses"] = [round(float(v.float().item()), 6) for v in losses]
@@ -228,6 +273,12 @@ def build_parser():
                          "kernels, out of place, relu and residual adds fused in the residual units) or inplace (HIP ABN "
                          "kernels writing over their input, gamma = |weight| + eps); when given, the JSON line also reports "
                          "abn, step_losses and max_memory_allocated_mb")
+    ap.add_argument("--device-augment", action="store_true",
+                    help="feed the step through the device input pipeline (ccnet_amd.augment): synthetic uint8 frames and "
+                         "Cityscapes id labels made once, each step's random scale 0.7 ... 2.1, pad, crop to --size, mirror and "
+                         "label remap done by one HIP kernel; composes with every criterion flag; needs a HIP device")
+    ap.add_argument("--augment-frame", type=int, nargs=2, default=[1024, 2048], metavar=("H", "W"),
+                    help="source frame size of --device-augment (Cityscapes: 1024 2048)")
     ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
     ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
