@@ -19,6 +19,8 @@ the same training step on random data, one process per GPU:
                the reference's scale, offsets and mirror and builds its batch with ccnet_amd.augment.DeviceAugment
                (dataset/datasets.py:173-210 as one HIP gather); composes with every criterion flag
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
+               --device-sgd: ccnet_amd.optim.DeviceSGD (the whole update, the gradient zeroing and the poly LR in one HIP
+               launch per step, the LR from a table on the device); composes with every other flag
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
                per-rank seed = rank                                                  train.py:154-155
 
@@ -146,19 +148,30 @@ def run(args, model_factory=None, quiet=False):
         extra = {"find_unused_parameters": True} if lovasz else {}
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if use_cuda else None,
                                                         broadcast_buffers=False, **extra)
-    opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.weight_decay)
+    total = args.warmup + args.steps
+    device_sgd = getattr(args, "device_sgd", False)
+    if device_sgd:
+        if not use_cuda:
+            raise RuntimeError("--device-sgd needs a HIP device (ccnet_amd has no CPU fallback for the optimiser kernels)")
+        from .optim import DeviceSGD, poly_schedule
+        # (the kernel zeroes the gradients and reads step k's LR from the table: no zero_grad() call and no LR loop below)
+        opt = DeviceSGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.weight_decay, zero_grads=True,
+                        schedule=poly_schedule(args.lr, max(total, 1)))
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.weight_decay)
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed + rank)
-    total = args.warmup + args.steps
 
     def step(it):
-        for g in opt.param_groups:
-            g["lr"] = lr_poly(args.lr, it, max(total, 1))
+        if not device_sgd:
+            for g in opt.param_groups:
+                g["lr"] = lr_poly(args.lr, it, max(total, 1))
         if source is not None:
             images, labels = source.next()
         else:
             images, labels = synthetic_batch(args.batch_per_gpu, args.size, args.num_classes, device, gen)
-        opt.zero_grad(set_to_none=True)
+        if not device_sgd:
+            opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.bf16 and use_cuda):
             loss = net(images, labels)
         loss.backward()
@@ -218,6 +231,8 @@ def run(args, model_factory=None, quiet=False):
             result["criterion"] = "lovasz-fused"
             if use_cuda:
                 result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
+        if device_sgd:
+            result["config"]["optimizer"] = "device-sgd+poly"
         if source is not None:
             result["data"] = "synthetic uint8 %d x %d frames through DeviceAugment" % source.frame
         if abn_mode is not None:
@@ -279,6 +294,11 @@ def build_parser():
                          "label remap done by one HIP kernel; composes with every criterion flag; needs a HIP device")
     ap.add_argument("--augment-frame", type=int, nargs=2, default=[1024, 2048], metavar=("H", "W"),
                     help="source frame size of --device-augment (Cityscapes: 1024 2048)")
+    ap.add_argument("--device-sgd", action="store_true",
+                    help="the optimiser step on the device (ccnet_amd.optim.DeviceSGD): momentum, weight decay, the zeroing of "
+                         "the gradients and the poly learning rate, read from a table on the device, in one HIP launch over "
+                         "every parameter; composes with every criterion flag, --abn, --bf16 and --device-augment; needs a HIP "
+                         "device; the JSON line then reports optimizer device-sgd+poly")
     ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
     ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
