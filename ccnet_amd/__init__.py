@@ -17,7 +17,7 @@ from .evaluate import MultiScaleEvaluator, SegEvaluator, predict_multiscale, pre
 from .lovasz import CriterionOhemDSN2, LovaszSoftmax, LovaszSoftmaxFunction, lovasz_softmax
 from .ohem import CriterionOhemDSN, OhemCrossEntropy2d
 from .ohemdsn import UpsampledOhemCrossEntropy2d, UpsampledOhemFunction
-from .optim import DeviceSGD, poly_schedule
+from .optim import DeviceMixedSGD, DeviceSGD, bf16_parameters, poly_schedule
 
 __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "ca_weight", "ca_map",
            "ca_softmax", "criss_cross_attention", "graph_module", "INF", "OhemCrossEntropy2d", "CriterionOhemDSN",
@@ -26,5 +26,6 @@ __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "
            "CriterionOhemDSN2", "ABN", "InPlaceABN", "InPlaceABNSync", "convert_abn", "UpsampledCrossEntropy2d",
            "UpsampledCrossEntropyFunction", "UpsampledOhemCrossEntropy2d", "UpsampledOhemFunction",
            "celovasz", "UpsampledCELovasz", "UpsampledCELovaszFunction", "augment", "DeviceAugment", "DevicePrefetcher",
-           "CSDataSet", "VOCDataSet", "AugmentParams", "draw_params", "CITYSCAPES_ID_TO_TRAINID", "DeviceSGD", "poly_schedule"]
+           "CSDataSet", "VOCDataSet", "AugmentParams", "draw_params", "CITYSCAPES_ID_TO_TRAINID", "DeviceSGD", "poly_schedule",
+           "DeviceMixedSGD", "bf16_parameters"]
 __version__ = "0.1.0"

@@ -21,6 +21,10 @@ the same training step on random data, one process per GPU:
     optimiser  SGD(lr 1e-2, momentum 0.9, weight decay 1e-4 ... 5e-4), poly LR      train.py:126-133,183
                --device-sgd: ccnet_amd.optim.DeviceSGD (the whole update, the gradient zeroing and the poly LR in one HIP
                launch per step, the LR from a table on the device); composes with every other flag
+               --bf16-params: bf16 parameters, gradients and images without autocast (ccnet_amd.optim.bf16_parameters; the
+               normalisation layers keep float32 affine parameters), both heads' logits cast to float32 in front of the
+               criterion, and ccnet_amd.optim.DeviceMixedSGD (float32 masters inside the one launch); refused with --bf16,
+               --device-sgd and --cpu
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
                per-rank seed = rank                                                  train.py:154-155
 
@@ -87,6 +91,17 @@ class AugmentedSource:
         return self.run(self.frames_dev, self.labels_dev, desc)
 
 
+class Float32Logits(torch.nn.Module):
+    """--bf16-params: the criterion behind a cast of every head's logits to float32 (the criteria's kernels take float32)"""
+
+    def __init__(self, criterion):
+        super().__init__()
+        self.criterion = criterion
+
+    def forward(self, preds, target):
+        return self.criterion([p.float() for p in preds], target)
+
+
 def run(args, model_factory=None, quiet=False):
     """One training job on the calling rank; returns the result dict (rank 0) or None.  ``quiet`` suppresses the
     JSON line (bench.py embeds the result in its own line)."""
@@ -138,6 +153,14 @@ def run(args, model_factory=None, quiet=False):
         from .abn import convert_abn
         convert_abn(model, abn_mode)
     model = model.to(device).train()
+    bf16_params = getattr(args, "bf16_params", False)
+    if bf16_params:
+        if not use_cuda:
+            raise RuntimeError("--bf16-params needs a HIP device (ccnet_amd has no CPU fallback for the optimiser kernels)")
+        from .optim import bf16_parameters
+        bf16_parameters(model)
+        if getattr(model, "criterion", None) is not None:
+            model.criterion = Float32Logits(model.criterion)
     if use_cuda and (abn_mode is not None or getattr(args, "fused_dsn", False) or getattr(args, "fused_ohem", False)
                      or getattr(args, "fused_lovasz", False)):
         torch.cuda.reset_peak_memory_stats(device)
@@ -150,7 +173,13 @@ def run(args, model_factory=None, quiet=False):
                                                         broadcast_buffers=False, **extra)
     total = args.warmup + args.steps
     device_sgd = getattr(args, "device_sgd", False)
-    if device_sgd:
+    if bf16_params:
+        from .optim import DeviceMixedSGD, poly_schedule
+        # (as with --device-sgd: the kernel zeroes the gradients and reads step k's LR from the table)
+        opt = DeviceMixedSGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.weight_decay, zero_grads=True,
+                             schedule=poly_schedule(args.lr, max(total, 1)))
+        device_sgd = True                                     # (for the step below: no zero_grad() call, no LR loop)
+    elif device_sgd:
         if not use_cuda:
             raise RuntimeError("--device-sgd needs a HIP device (ccnet_amd has no CPU fallback for the optimiser kernels)")
         from .optim import DeviceSGD, poly_schedule
@@ -170,6 +199,8 @@ def run(args, model_factory=None, quiet=False):
             images, labels = source.next()
         else:
             images, labels = synthetic_batch(args.batch_per_gpu, args.size, args.num_classes, device, gen)
+        if bf16_params:
+            images = images.to(torch.bfloat16)
         if not device_sgd:
             opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.bf16 and use_cuda):
@@ -209,7 +240,7 @@ def run(args, model_factory=None, quiet=False):
             "value": round(args.steps * args.batch_per_gpu * world / elapsed, 3), "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / max(args.steps, 1) * 1e3, 2), "scaling": "weak",
-            "dtype": "bf16-autocast" if args.bf16 else "f32", "data": "synthetic",
+            "dtype": "bf16-params" if bf16_params else "bf16-autocast" if args.bf16 else "f32", "data": "synthetic",
             "config": {"image": [3, args.size, args.size], "per_gpu_batch": args.batch_per_gpu,
                        "global_batch": args.batch_per_gpu * world, "parallelism": f"ddp{world}+syncbn",
                        "optimizer": "sgd+poly"},
@@ -232,7 +263,7 @@ def run(args, model_factory=None, quiet=False):
             if use_cuda:
                 result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
         if device_sgd:
-            result["config"]["optimizer"] = "device-sgd+poly"
+            result["config"]["optimizer"] = "device-mixed-sgd+poly" if bf16_params else "device-sgd+poly"
         if source is not None:
             result["data"] = "synthetic uint8 %d x %d frames through DeviceAugment" % source.frame
         if abn_mode is not None:
@@ -299,6 +330,12 @@ def build_parser():
                          "the gradients and the poly learning rate, read from a table on the device, in one HIP launch over "
                          "every parameter; composes with every criterion flag, --abn, --bf16 and --device-augment; needs a HIP "
                          "device; the JSON line then reports optimizer device-sgd+poly")
+    ap.add_argument("--bf16-params", action="store_true",
+                    help="bf16 parameters and gradients with float32 masters in the optimiser (ccnet_amd.optim.bf16_parameters + "
+                         "DeviceMixedSGD, one HIP launch per step with the zeroing and the poly learning rate): bf16 images, no "
+                         "autocast, the normalisation layers' parameters and both heads' logits in float32; refused with "
+                         "--bf16, --device-sgd and --cpu; needs a HIP device; the JSON line then reports dtype bf16-params and "
+                         "optimizer device-mixed-sgd+poly")
     ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
     ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
@@ -309,7 +346,17 @@ def build_parser():
 
 
 def check_args(args):
-    """Combinations the criteria cannot serve; raises ValueError."""
+    """Combinations the criteria and the optimisers cannot serve; raises ValueError."""
+    if getattr(args, "bf16_params", False):
+        if getattr(args, "bf16", False):
+            raise ValueError("--bf16-params cannot be combined with --bf16: the parameters are bf16 already and nothing is left "
+                             "for autocast to cast")
+        if getattr(args, "device_sgd", False):
+            raise ValueError("--bf16-params cannot be combined with --device-sgd: DeviceSGD takes float32 parameters only, "
+                             "--bf16-params brings DeviceMixedSGD")
+        if getattr(args, "cpu", False):
+            raise ValueError("--bf16-params cannot be combined with --cpu: it needs a HIP device (ccnet_amd has no CPU fallback "
+                             "for the optimiser kernels)")
     if getattr(args, "fused_dsn", False) and getattr(args, "lovasz", False):
         raise ValueError("--fused-dsn cannot be combined with --lovasz: CriterionOhemDSN2 takes the Lovász-softmax of the "
                          "full-resolution map and leaves the DSN head unused")
