@@ -10,6 +10,7 @@ from .abn import ABN, InPlaceABN, InPlaceABNSync, convert_abn
 from .augment import (CITYSCAPES_ID_TO_TRAINID, AugmentParams, CSDataSet, DeviceAugment, DevicePrefetcher, VOCDataSet,
                       draw_params)
 from .celovasz import UpsampledCELovasz, UpsampledCELovaszFunction
+from .conv3 import DeviceConv3x3, conv3x3, convert_conv3x3
 from .dsn import UpsampledCrossEntropy2d, UpsampledCrossEntropyFunction
 from .functions import (CA_Map, CA_Weight, CrissCrossAttention, CrissCrossFunction, INF, ca_map, ca_softmax,
                         ca_weight, criss_cross_attention, graph_module)
@@ -27,5 +28,5 @@ __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "
            "UpsampledCrossEntropyFunction", "UpsampledOhemCrossEntropy2d", "UpsampledOhemFunction",
            "celovasz", "UpsampledCELovasz", "UpsampledCELovaszFunction", "augment", "DeviceAugment", "DevicePrefetcher",
            "CSDataSet", "VOCDataSet", "AugmentParams", "draw_params", "CITYSCAPES_ID_TO_TRAINID", "DeviceSGD", "poly_schedule",
-           "DeviceMixedSGD", "bf16_parameters"]
+           "DeviceMixedSGD", "bf16_parameters", "conv3x3", "DeviceConv3x3", "convert_conv3x3"]
 __version__ = "0.1.0"

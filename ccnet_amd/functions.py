@@ -1007,11 +1007,11 @@ class CrissCrossAttention(nn.Module):
                 #  fp32 module under autocast: autocast does NOT govern them, unlike the reference's autocast convolutions)
                 y = CrissCrossPlanesModuleFunction.apply(x.float().contiguous(), *(p.float() for p in params), self.gamma.float(),
                                                          split_gemm, self.recompute_attention)
-            return y.to(x.dtype)
+            return _cast_like(y, x)
         proj_query, proj_key, proj_value = self.query_conv(x), self.key_conv(x), self.value_conv(x)
         out = CrissCrossFunction.apply(proj_query.float(), proj_key.float(), proj_value.float(),
                                        x.float(), self.gamma.float(), self.recompute_attention)
-        return out.to(x.dtype)
+        return _cast_like(out, x)
 
     def _library_projections_ok(self, x, B, C, cq, H, W):
         """``ccnet_proj_gemm_bf16``'s contract for this input, and parameters it packs: bf16, or fp32 under a bf16 autocast"""
@@ -1049,6 +1049,14 @@ class CrissCrossAttention(nn.Module):
         if x is not None:
             return all(c.weight.device == x.device and c.weight.dtype == x.dtype for c in convs) and x.shape[1] == cin
         return len({(c.weight.device, c.weight.dtype) for c in convs}) == 1
+
+
+def _cast_like(y, x):
+    """``y`` (fp32) in ``x``'s dtype.  Where that cast copies anyway and ``x`` is channels_last, the copy is written in ``x``'s
+    memory format, as the pixel-major and split-plane routes return theirs: a channels_last network stays channels_last."""
+    if y.dtype != x.dtype and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+        return y.to(x.dtype, memory_format=torch.channels_last)
+    return y.to(x.dtype)
 
 
 def graph_module(module: "CrissCrossAttention", sample_input: torch.Tensor, warmup_iters: int = 3):

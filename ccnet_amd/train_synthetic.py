@@ -25,6 +25,10 @@ the same training step on random data, one process per GPU:
                normalisation layers keep float32 affine parameters), both heads' logits cast to float32 in front of the
                criterion, and ccnet_amd.optim.DeviceMixedSGD (float32 masters inside the one launch); refused with --bf16,
                --device-sgd and --cpu
+    convs      --device-conv3: every eligible 3x3 convolution (stride 1, padding == dilation) swapped for the library's implicit
+               GEMM (ccnet_amd.conv3.convert_conv3x3), the images -- and with the stock optimiser the model -- in
+               torch.channels_last (DeviceSGD and DeviceMixedSGD walk contiguous parameters: there the activations alone
+               carry the format); needs --bf16 or --bf16-params; refused with --abn device|inplace (NCHW-only layers) and --cpu
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
                per-rank seed = rank                                                  train.py:154-155
 
@@ -152,7 +156,25 @@ def run(args, model_factory=None, quiet=False):
     if abn_mode in ("device", "inplace"):
         from .abn import convert_abn
         convert_abn(model, abn_mode)
+    device_conv3 = getattr(args, "device_conv3", False)
+    if device_conv3:
+        if not use_cuda:
+            raise RuntimeError("--device-conv3 needs a HIP device (ccnet_amd has no CPU fallback for the convolution kernels)")
+        from .conv3 import convert_conv3x3, native_batch_norm_for_bf16_channels_last
+        converted = convert_conv3x3(model)
+        # (the stock normalisation layers now see bf16 channels_last activations: conv3.NativeChannelsLast says what that needs)
+        native_batch_norm_for_bf16_channels_last(model)
     model = model.to(device).train()
+    if device_conv3:
+        # the activations carry the format from the images on (a convolution's output follows a channels_last input).  The
+        # parameters follow only where the optimiser takes strided ones: DeviceSGD and DeviceMixedSGD walk contiguous memory, and
+        # the converted layers pack their weight from the parameter's own (Cout, Cin, 3, 3) layout
+        if not (getattr(args, "bf16_params", False) or getattr(args, "device_sgd", False)):
+            from .conv3 import DeviceConv3x3
+            model = model.to(memory_format=torch.channels_last)
+            for m in model.modules():
+                if isinstance(m, DeviceConv3x3):
+                    m.weight.data = m.weight.data.contiguous()
     bf16_params = getattr(args, "bf16_params", False)
     if bf16_params:
         if not use_cuda:
@@ -201,6 +223,8 @@ def run(args, model_factory=None, quiet=False):
             images, labels = synthetic_batch(args.batch_per_gpu, args.size, args.num_classes, device, gen)
         if bf16_params:
             images = images.to(torch.bfloat16)
+        if device_conv3:
+            images = images.contiguous(memory_format=torch.channels_last)
         if not device_sgd:
             opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.bf16 and use_cuda):
@@ -264,6 +288,9 @@ def run(args, model_factory=None, quiet=False):
                 result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
         if device_sgd:
             result["config"]["optimizer"] = "device-mixed-sgd+poly" if bf16_params else "device-sgd+poly"
+        if device_conv3:
+            result["config"]["conv3"] = "device"
+            result["config"]["conv3_layers"] = converted
         if source is not None:
             result["data"] = "synthetic uint8 %d x %d frames through DeviceAugment" % source.frame
         if abn_mode is not None:
@@ -336,6 +363,11 @@ def build_parser():
                          "autocast, the normalisation layers' parameters and both heads' logits in float32; refused with "
                          "--bf16, --device-sgd and --cpu; needs a HIP device; the JSON line then reports dtype bf16-params and "
                          "optimizer device-mixed-sgd+poly")
+    ap.add_argument("--device-conv3", action="store_true",
+                    help="every eligible 3x3 convolution (stride 1, padding == dilation, groups 1, channel counts divisible by 8) "
+                         "on the library's implicit-GEMM kernels (ccnet_amd.conv3.convert_conv3x3), the images (and, with the stock "
+                         "optimiser, the model) in torch.channels_last; needs --bf16 or --bf16-params; refused with --abn device|inplace, whose layers are "
+                         "NCHW-only, and with --cpu; the JSON line then reports config.conv3 device")
     ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
     ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
@@ -357,6 +389,15 @@ def check_args(args):
         if getattr(args, "cpu", False):
             raise ValueError("--bf16-params cannot be combined with --cpu: it needs a HIP device (ccnet_amd has no CPU fallback "
                              "for the optimiser kernels)")
+    if getattr(args, "device_conv3", False):
+        if not (getattr(args, "bf16", False) or getattr(args, "bf16_params", False)):
+            raise ValueError("--device-conv3 needs --bf16 or --bf16-params: the convolution kernels take bf16 activations")
+        if getattr(args, "abn", None) in ("device", "inplace"):
+            raise ValueError("--device-conv3 cannot be combined with --abn device|inplace: the device ABN layers are NCHW-only, "
+                             "the convolution kernels channels_last")
+        if getattr(args, "cpu", False):
+            raise ValueError("--device-conv3 cannot be combined with --cpu: it needs a HIP device (ccnet_amd has no CPU fallback "
+                             "for the convolution kernels)")
     if getattr(args, "fused_dsn", False) and getattr(args, "lovasz", False):
         raise ValueError("--fused-dsn cannot be combined with --lovasz: CriterionOhemDSN2 takes the Lovász-softmax of the "
                          "full-resolution map and leaves the DSN head unused")
