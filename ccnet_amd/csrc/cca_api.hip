@@ -77,6 +77,36 @@ inline int cache_order(int bit) {
     const int v = g_cache_order.load();
     return ((v < 0 ? kCacheOrderShipped : v) & bit) ? 1 : 0;
 }
+// "stream_policy": the cache policy of the C-sized streams of the split-plane step (strips <= 100; cca_policy.hpp): which of them are
+// read and written NON-TEMPORALLY -- a last use, or an output nobody reads again, then does not compete for the 256 MiB of Infinity
+// Cache with the tensors the next launch re-reads.  The kernels, their instruction streams and their results are those of the
+// default policy; only where a line is kept changes (tests/test_isa_stream_policy.py).  A bit mask, one bit per (launch, operand
+// class) of the A/B that chose it (tools/ab_options.py "policy-*", profiles/stream_policy_*.txt):
+//   bit 1   forward NCHW row pass: its v, partial and x loads are non-temporal
+//   bit 8   dv row pass: its dy-plane and partial loads        bit 9   dv row pass: its dv stores
+//           (a kernel has ONE instantiation beside the default one: bits 8 and 9 take effect together)
+// Bits 0, 2 - 7, 10 - 13 were the candidates that lost (write-through stores of the partials, y, the planes, dv and dq | dk; nt on
+// the y and dq | dk stores, on dy, on dA's v and on the dq | dk partial): their variants are gone, the bits are accepted and ignored.
+// 0 = every access exactly as before the option, -1 (default) = the shipped mask.  Attention-shaped tensors, the three-plane row
+// passes, the bf16 family and strips > 100 always run the default policy.  Read on the host at launch time: a captured graph
+// keeps what was set at capture.
+// Shipped: all three.  Same-run A/B at (8,512,97,97), graph replay, against mask 0 over seven rounds: 0.6711 vs 0.7127 ms, below
+// mask 0 in every round, gain 41.6 us against 21.5 us of spread over the rounds (the box changed its clock state once); the mask
+// without any one of its bits gains 27 - 31 us (profiles/stream_policy_union.txt).
+constexpr int kStreamPolicyShipped = 770;
+std::atomic<int> g_stream_policy{-1};
+enum { SPB_L4_LD_NT = 1 << 1, SPB_L8_LD_NT = 1 << 8, SPB_L8_ST_NT = 1 << 9, SPB_ALL = (1 << 14) - 1 };
+// the kernel policy of a launch: ``pol`` (cca::SP_*) when every bit of ``bits`` is set, else the default one
+inline int stream_policy(int bits, int pol) {
+    const int v = g_stream_policy.load();
+    return ((v < 0 ? kStreamPolicyShipped : v) & bits) == bits ? pol : 0;
+}
+// calls ``launch`` with the policy as a compile-time constant: the default instantiation or the launch site's other one
+template <int POL, typename F>
+void with_policy(int pol, F &&launch) {
+    if (pol == POL) launch(std::integral_constant<int, POL>{});
+    else launch(std::integral_constant<int, 0>{});
+}
 // "da_stages": ring stages of the persistent dA kernel (plane-free form).  Three fill the CU's LDS (159,744 B): the dv column pass on
 // the side stream could not place a single workgroup next to it and in fact WAITED for the dA workgroups to exit (kernel-trace
 // timeline: its 69 us of work spanned 223 us).  With two stages (106,496 B) one 53,248-byte column workgroup fits per CU and the two
@@ -1193,6 +1223,16 @@ int launch_gmap_planes_row_p(const float *T, const bf16p_t *F, const float *resi
     cca::GmapJob<bf16p_t, float> job{};
     if (NCHW) nchw_row_decode(job, B, H, gr.n_whole, P <= 100 && !TRANS);
     else if (P <= 100 && TRANS) job.order = cache_order(ORDER_L8);      // (the dv row pass)
+    if constexpr (P <= 100 && TRANS && !NCHW) {                          // (the dv row pass: "stream_policy")
+        constexpr int NT = cca::SP_FEAT_NT | cca::SP_ADD_NT | cca::SP_ST_NT;
+        with_policy<NT>(stream_policy(SPB_L8_LD_NT | SPB_L8_ST_NT, NT), [&](auto pol) {
+            constexpr int POL = decltype(pol)::value;
+            CCA_LAUNCH((cca::gmap_kernel<P, true, TRANS, true, bf16p_t, float, NCHW, false, WPC, false, false, false, false, POL>), dim3((unsigned)gr.grid),
+                       dim3(cca::GS_THREADS), stream, T, F, (const float *)partial, resid, gamma, out, C, H, W, fbs, fps, pbs, C, rbs, rps, obs, ops,
+                       gr.n_whole, gr.split, job);
+        });
+        return launch_status("gmap_planes(row)");
+    }
     CCA_LAUNCH((cca::gmap_kernel<P, true, TRANS, true, bf16p_t, float, NCHW, false, WPC>), dim3((unsigned)gr.grid), dim3(cca::GS_THREADS),
                stream, T, F, (const float *)partial, resid, gamma, out, C, H, W, fbs, fps, pbs, C, rbs, rps, obs, ops,
                gr.n_whole, gr.split, job);
@@ -1308,9 +1348,13 @@ int launch_gmap_direct_f32(const float *T, const float *v, const float *resid, c
     if (int e = launch_status("gmap3_direct(column)")) return e;
     cca::GmapJob<float, float> job{};
     nchw_row_decode(job, B, H, gr.n_whole);
-    CCA_LAUNCH((cca::gmap_kernel<100, true, false, true, float, float, true, false, 2>), dim3((unsigned)gr.grid), dim3(cca::GS_THREADS),
-               stream, T, v, (const float *)partial, resid, gamma, out, C, H, W, fbs, fps, pbs, C, rbs, 0, obs, 0,
-               gr.n_whole, gr.split, job);
+    constexpr int NT = cca::SP_FEAT_NT | cca::SP_ADD_NT | cca::SP_SRC_NT;       // ("stream_policy": v, the partial and x are last uses)
+    with_policy<NT>(stream_policy(SPB_L4_LD_NT, NT), [&](auto pol) {
+        constexpr int POL = decltype(pol)::value;
+        CCA_LAUNCH((cca::gmap_kernel<100, true, false, true, float, float, true, false, 2, false, false, false, false, POL>), dim3((unsigned)gr.grid),
+                   dim3(cca::GS_THREADS), stream, T, v, (const float *)partial, resid, gamma, out, C, H, W, fbs, fps, pbs, C, rbs, 0, obs, 0,
+                   gr.n_whole, gr.split, job);
+    });
     return launch_status("gmap_direct(row)");
 }
 // strips 101 .. 132 with fp32 q | k: the energies and dq | dk kernels of the pixel-major fp32 family at 132 positions (one
@@ -1777,6 +1821,7 @@ const OptionRange *find_word_option(const std::string &n) {
         {"planes_overlap", &g_planes_overlap, -1, 2},
         {"planes_xcd", &g_planes_xcd, 0, 1},
         {"cache_order", &g_cache_order, -1, 63},
+        {"stream_policy", &g_stream_policy, -1, SPB_ALL},
         {"energy_tail", &g_energy_tail, 0, 1},
         {"dqdk_wpc3", &g_dqdk_wpc3, 0, 1},
         {"da_stages", &g_da_stages, 2, 3},

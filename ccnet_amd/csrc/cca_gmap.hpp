@@ -29,6 +29,7 @@
 // vmcnt).  Measured (profiles/r02f_*): the 512-channel launches move their bytes at 4.2 - 4.6 TB/s.
 #pragma once
 #include "cca_common.hpp"
+#include "cca_policy.hpp"
 
 #include <type_traits>
 
@@ -71,15 +72,16 @@ struct GTile {
 // one DMA piece of a pixel-major tile: pixels pix0 + i * pstep (i < n), channels c0 .. c0 + 63 of a tensor with
 // pixel stride ps (elements of FT); lane -> (pixel, 16-byte chunk).  Lanes beyond the strip / the channel count are
 // issued out of range: the DMA deposits zeros for them, so a tile is complete (and finite) after every fill
-template <typename FT>
+// (CP: the cache policy of the fill, cca_policy.hpp -- here and in t16_dma_piece)
+template <typename FT, int CP = CP_DEFAULT>
 __device__ __forceinline__ void gtile_dma_piece(const FBuf &src, float *img, int piece, int lane, int pix0, int pstep, int n,
                                                 int ps, int c0, int C, int plane_off = 0) {
     if constexpr (GTile<FT>::BF) {
         const int p = lane >> 3, i = 8 * piece + p, q = (lane & 7) ^ (p & 7), c = c0 + 8 * q;
-        fbuf_load_to_lds_x4_uncounted(src, img + piece * GM_PB, (i < n && c < C) ? ((pix0 + i * pstep) * ps + plane_off + c) * 2 : kOobOffset);
+        fbuf_load_to_lds_x4_uncounted_cp<CP>(src, img + piece * GM_PB, (i < n && c < C) ? ((pix0 + i * pstep) * ps + plane_off + c) * 2 : kOobOffset);
     } else {
         const int i = 4 * piece + (lane >> 4), c = c0 + 4 * ((lane & 15) ^ (i & 1));
-        fbuf_load_to_lds_x4_uncounted(src, img + piece * GM_PP, (i < n && c < C) ? ((pix0 + i * pstep) * ps + c) * 4 : kOobOffset);
+        fbuf_load_to_lds_x4_uncounted_cp<CP>(src, img + piece * GM_PP, (i < n && c < C) ? ((pix0 + i * pstep) * ps + c) * 4 : kOobOffset);
     }
 }
 // fp32 tiles: 4 pixels x 64 channels per 1 KiB DMA piece; the 16-byte chunk q of pixel p sits at chunk position
@@ -125,11 +127,11 @@ __device__ __forceinline__ int t16_byte(int j, int c) {
 // one DMA piece of a plane tile: positions 8 piece .. + 7 (pixels pix0 + i * pstep), channels c0 .. c0 + 63 of the plane
 // that starts ``plane_off`` elements into a pixel; ps = pixel stride in elements; lanes beyond the strip / the channel
 // count fetch out of range (zero fill)
-template <bool FLIP = true>
+template <bool FLIP = true, int CP = CP_DEFAULT>
 __device__ __forceinline__ void t16_dma_piece(const FBuf &src, float *img, int piece, int lane, int pix0, int pstep, int n,
                                               int ps, int c0, int C, int plane_off) {
     const int p = lane >> 3, i = 8 * piece + p, q = (lane & 7) ^ (p & 7) ^ (FLIP ? (piece & 1) << 2 : 0), c = c0 + 8 * q;
-    fbuf_load_to_lds_x4_uncounted(src, img + piece * T16_PIECE, (i < n && c < C) ? ((pix0 + i * pstep) * ps + plane_off + c) * 2 : kOobOffset);
+    fbuf_load_to_lds_x4_uncounted_cp<CP>(src, img + piece * T16_PIECE, (i < n && c < C) ? ((pix0 + i * pstep) * ps + plane_off + c) * 2 : kOobOffset);
 }
 // MFMA fragment whose K axis runs over tile positions 32 ks + 8 (lane >> 4) + e, e < 8, at channel 16 nt + (lane & 15):
 // two transposing reads (cca_platform.hpp: lane i of a 16-lane group supplies the address of row i >> 2, columns
@@ -223,7 +225,7 @@ inline unsigned gmap_dual_grid(int nwg) { return 16u * (unsigned)((nwg + 7) / 8)
 // features, whose two feature tiles + output image take 104 KB: one workgroup per CU)
 // ABF (bf16 features, round 5): the addend -- the column partial -- is bf16 (see gmap3_kernel, OT): one 16-byte load of 8 channels
 template <int P, bool ROW, bool TRANS, bool ADD, typename FT, typename OT, bool NCHW = false, bool DUAL = false, int WPC = 2, bool LONG = false,
-          bool SIX = false, bool ABF = false, bool P3 = false>
+          bool SIX = false, bool ABF = false, bool P3 = false, int POL = 0>
 __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__restrict__ T, const FT *__restrict__ F,
                                                               const float *__restrict__ addend,
                                                               const OT *__restrict__ resid,
@@ -233,6 +235,10 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
                                                               GmapJob<FT, OT> j1) {
     constexpr bool BF = GTile<FT>::BF, OBF = std::is_same<OT, bf16_t>::value;
     constexpr bool PL = std::is_same<FT, bf16p_t>::value;             // split planes: hi tile | lo tile, T16 geometry
+    // POL (option "stream_policy", cca_policy.hpp): the cache policy of the feature fills, the addend and residual loads and the
+    // 16-byte output stores (0 everywhere but in the two row passes of the split-plane step); the attention block, the
+    // three-plane stores and the column sums keep the default
+    constexpr int CPF = sp_load(POL, SP_FEAT_NT), CPA = sp_load(POL, SP_ADD_NT), CPR = sp_load(POL, SP_SRC_NT), CPS = sp_store(POL);
     // SIX (option "dqdk_exact", the default of ca_backward on fp32 q | k): every product as the SIX bf16 terms of a three-way split
     // (bf16_split8x3) -- fp32-equivalent (2^-24), where the three-term form leaves ~1.2e-5 of the gradient's magnitude on dq / dk
     // (tests: logit-scale sweep) -- at 3/8 of the matrix time of v_mfma_f32_16x16x4_f32.  The attention block stays in registers
@@ -362,10 +368,10 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
         for (int it = wv; it < NPF; it += GS_WAVES) {
             if constexpr (PL) {
                 const int plane = it >= NPF / 2;
-                t16_dma_piece(Fb, FB + ((cg - cg0) & 1) * FSZ + plane * TSP, it - plane * (NPF / 2), lane, pixK, pstep, Lk, fps,
+                t16_dma_piece<true, CPF>(Fb, FB + ((cg - cg0) & 1) * FSZ + plane * TSP, it - plane * (NPF / 2), lane, pixK, pstep, Lk, fps,
                               cg * GM_CG, C, plane ? C : 0);
             } else {
-                gtile_dma_piece<FT>(Fb, FB + (ONEG ? 0 : (cg - cg0) & 1) * FSZ, it, lane, pixK, pstep, Lk, fps, cg * GM_CG, C);
+                gtile_dma_piece<FT, CPF>(Fb, FB + (ONEG ? 0 : (cg - cg0) & 1) * FSZ, it, lane, pixK, pstep, Lk, fps, cg * GM_CG, C);
             }
         }
     };
@@ -438,14 +444,14 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) {
                     const int c = cg * GM_CG + 16 * nt + 4 * lg;
-                    addp[a][nt] = fbuf_load_x4(Db, (i < Lm && c < C) ? ((pixM + i) * aps + c) * 4 : kOobOffset, 0);
+                    addp[a][nt] = fbuf_load_x4_cp<CPA>(Db, (i < Lm && c < C) ? ((pixM + i) * aps + c) * 4 : kOobOffset, 0);
                 }
             }
 #pragma unroll
             for (int k = 0; k < NSX; ++k) {                 // residual in the store layout: 4 positions of channel c
                 const int c = cg * GM_CG + CPI * (wv + GS_WAVES * k) + (lane / LPC), w4 = lane & (LPC - 1);
                 const int w0 = (4 * w4 + 3 < Lm || Lm < 4) ? 4 * w4 : Lm - 4;      // the last granule is shifted back to end at Lm
-                resx[k] = fbuf_load_x4(Rb, (resid && 4 * w4 < Lm && c < C) ? (c * HW + pixM + w0) * 4 : kOobOffset, 0);
+                resx[k] = fbuf_load_x4_cp<CPR>(Rb, (resid && 4 * w4 < Lm && c < C) ? (c * HW + pixM + w0) * 4 : kOobOffset, 0);
             }
         }
 #pragma unroll
@@ -455,7 +461,7 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
             const int pix = pixM + i * pstep;
             if (ADD && !X6) {                             // (X6: the addend starts the accumulators, see below)
                 if constexpr (ABF) {                      // 8 bf16 channels of the partial -> two fp32 quads
-                    const u32x4 pk = __builtin_bit_cast(u32x4, fbuf_load_x4(Db, ok ? (pix * aps + c) * 2 : kOobOffset, 0));
+                    const u32x4 pk = __builtin_bit_cast(u32x4, fbuf_load_x4_cp<CPA>(Db, ok ? (pix * aps + c) * 2 : kOobOffset, 0));
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
                         add0[k][2 * e] = __builtin_bit_cast(float, pk[e] << 16);
@@ -464,11 +470,11 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
                         add1[k][2 * e + 1] = __builtin_bit_cast(float, pk[2 + e] & 0xffff0000u);
                     }
                 } else {
-                add0[k] = fbuf_load_x4(Db, ok ? (pix * aps + c) * 4 : kOobOffset, 0);
-                if (OBF) add1[k] = fbuf_load_x4(Db, ok ? (pix * aps + c + 4) * 4 : kOobOffset, 0);
+                add0[k] = fbuf_load_x4_cp<CPA>(Db, ok ? (pix * aps + c) * 4 : kOobOffset, 0);
+                if (OBF) add1[k] = fbuf_load_x4_cp<CPA>(Db, ok ? (pix * aps + c + 4) * 4 : kOobOffset, 0);
                 }
             }
-            if constexpr (RES) res[k] = __builtin_bit_cast(u32x4, fbuf_load_x4(Rb, (ok && resid) ? (pix * rps + c) * (int)sizeof(OT) : kOobOffset, 0));
+            if constexpr (RES) res[k] = __builtin_bit_cast(u32x4, fbuf_load_x4_cp<CPR>(Rb, (ok && resid) ? (pix * rps + c) * (int)sizeof(OT) : kOobOffset, 0));
         }
         // D^T[m = channel][n = strip position] = features^T x attention^T: a lane ends up with 4 consecutive channels of
         // one position (one ds_write_b128 into the pixel-major output image)
@@ -486,7 +492,7 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
                 for (int n = 0; n < NTH; ++n) {
                     if constexpr (X6 && ADD) {
                         const int i = 16 * (wv + GS_WAVES * a) + ln, c = cg * GM_CG + 16 * (nh * NTH + n) + 4 * lg;
-                        acc[a][n] = fbuf_load_x4(Db, (i < Lm && c < C) ? ((pixM + i * pstep) * aps + c) * 4 : kOobOffset, 0);
+                        acc[a][n] = fbuf_load_x4_cp<CPA>(Db, (i < Lm && c < C) ? ((pixM + i * pstep) * aps + c) * 4 : kOobOffset, 0);
                     } else {
                         acc[a][n] = f32x4{0.f, 0.f, 0.f, 0.f};
                     }
@@ -615,7 +621,7 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
 #pragma unroll
                             for (int e = 0; e < 4; ++e) u[e] = CCA_LDS_LD(oimg + oimg_nchw_idx<P>(ch, (4 * w4 < Lm ? w0 : 0) + e));
                         }
-                        if (4 * w4 < Lm && c < C) fbuf_store_x4(Ob, u + resx[k], (c * HW + pixM + w0) * 4, 0);
+                        if (4 * w4 < Lm && c < C) fbuf_store_x4_cp<CPS>(Ob, u + resx[k], (c * HW + pixM + w0) * 4, 0);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 3; ++e) {
@@ -651,7 +657,7 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
                         }
                         const f32x4 packed = __builtin_bit_cast(f32x4, u32x4{cvt_pk_bf16(u[0], u[1]), cvt_pk_bf16(u[2], u[3]),
                                                                              cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])});
-                        fbuf_store_x4(Ob, packed, ((pixM + i * pstep) * ops + c) * 2, 0);
+                        fbuf_store_x4_cp<CPS>(Ob, packed, ((pixM + i * pstep) * ops + c) * 2, 0);
                     } else {
                         if constexpr (RES) u += __builtin_bit_cast(f32x4, res[k]);          // (+ the fp32 residual; zeros when there is none)
                         if constexpr (P3) {
@@ -664,7 +670,7 @@ __global__ __launch_bounds__(GS_THREADS, WPC) void gmap_kernel(const float *__re
                             fbuf_store_x2(Ob, l0, l1, off + 2 * j1.p3_plane, 0);
                             fbuf_store_x2(Ob, h0, h1, off + 4 * j1.p3_plane, 0);
                         } else
-                        fbuf_store_x4(Ob, u, ((pixM + i * pstep) * ops + c) * 4, 0);
+                        fbuf_store_x4_cp<CPS>(Ob, u, ((pixM + i * pstep) * ops + c) * 4, 0);
                     }
                 }
             }

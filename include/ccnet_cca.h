@@ -391,6 +391,12 @@ int ccnet_cca_backward_planes3_f32(const float *dy, const float *q, const float 
  *                    descending; it needs what "planes_xcd" needs and B % 8 == 0, else today's decode runs, reversed if asked).
  *                    0 = the traversal as it always was; -1 (default) = the shipped pattern.  Only moves workgroups: same bits.
  *                    Read at launch time: a captured graph keeps the value it was captured with.
+ *   "stream_policy" the cache policy of the C-sized streams of the split-plane step (strips <= 100): a bit mask of the streams that are
+ *                    read / written non-temporally -- last uses and outputs nobody reads again, which then do not compete for the
+ *                    Infinity Cache with what the next launch re-reads.  2 = the v, partial and x loads of the forward NCHW row
+ *                    pass; 256 | 512 (together) = the dy-plane and partial loads and the dv stores of the dv row pass.  The other
+ *                    bits below 2^14 are accepted and ignored (candidates that lost their A/B).  0 = every access as before the
+ *                    option; -1 (default) = the shipped mask (770).  Same instructions, same bits; read at launch time.
  *   "da_stages"    2 (default) / 3: LDS ring stages of the persistent dA kernel of the plane-free backward.  Three fill the CU's LDS,
  *                    so the dv column pass on the side stream waits for its workgroups to exit; two leave room for one column
  *                    workgroup per CU and the launches overlap for real (backward 0.45 -> 0.40 ms at the headline shape).

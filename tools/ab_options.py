@@ -5,7 +5,11 @@ every launch on one stream -- the per-launch durations.
 The "order-*" sets are the A/B of option "cache_order" (which streaming launches walk the images in descending order):
 a mask WINS only if its graph-replay step is below order-0's in EVERY round and its mean gain exceeds the largest difference
 between two rounds of one set -- the run's own noise; the closing table says so per set.
-usage: ab_options.py [B C H W] [--sets name,name,... ("order": every order-* set; "order-mNN": mask NN)] [--rounds N]"""
+The "policy-*" sets are the A/B of option "stream_policy" (the cache policy of the step's C-sized streams): "policy-0"
+is the step of before the option, "policy-<name>" one live bit (bits 8 and 9 act together: one set), "policy-mNN" the mask NN,
+"policy-shipped" the library's default; the same table and the same win rule, against policy-0.
+usage: ab_options.py [B C H W] [--sets name,name,... ("order": every order-* set; "order-mNN": mask NN; "policy": policy-0 and
+       every live bit; "policy-mNN")] [--rounds N]"""
 import os
 import sys
 
@@ -41,19 +45,29 @@ DEFAULT_SETS = {
     "order-L4-xcd": {"cache_order": 32},
     "order-model-no-xcd": {"cache_order": 14, "planes_xcd": 0},
     "order-complement": {"cache_order": 17},                    # L3 and L8 descending, L4, L6, L7 ascending
+    # "stream_policy": one bit per (launch, operand class), cca_api.hip
+    "policy-0": {"stream_policy": 0},                           # every access as before the option
+    "policy-shipped": {"stream_policy": -1},
+    "policy-L4-loads-nt": {"stream_policy": 1 << 1},            # forward NCHW row pass: v, partial, x loads non-temporal
+    "policy-L8-nt": {"stream_policy": 3 << 8},                  # dv row pass: plane and partial loads, dv stores non-temporal
 }
 if "--sets" in sys.argv:
     keep = sys.argv[sys.argv.index("--sets") + 1].split(",")
     for k in keep:                                      # "order-mNN": any other mask of "cache_order"
         if k.startswith("order-m") and k[7:].isdigit():
             DEFAULT_SETS[k] = {"cache_order": int(k[7:])}
-    DEFAULT_SETS = {k: v for k, v in DEFAULT_SETS.items() if k in keep or k == "default" or ("order" in keep and k.startswith("order-"))}
+        if k.startswith("policy-m") and k[8:].isdigit():
+            DEFAULT_SETS[k] = {"stream_policy": int(k[8:])}
+    DEFAULT_SETS = {k: v for k, v in DEFAULT_SETS.items() if k in keep or k == "default" or ("order" in keep and k.startswith("order-"))
+                    or ("policy" in keep and k.startswith("policy-"))}
+else:
+    DEFAULT_SETS = {k: v for k, v in DEFAULT_SETS.items() if not k.startswith("policy-")}      # (the policy A/B runs when asked for)
 ROUNDS = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 2
-DETAIL = ("one-stream", "dqdk-three-terms") + tuple(k for k in DEFAULT_SETS if k.startswith("order-"))
+DETAIL = ("one-stream", "dqdk-three-terms") + tuple(k for k in DEFAULT_SETS if k.startswith(("order-", "policy-")))
 lib = _lib.get_lib()
 dev = torch.device("cuda:0")
 BASE = {"planes_ring": 2, "planes_stream": 1, "planes_overlap": -1, "planes_xcd": 1, "energy_tail": 1, "da_stages": 2, "dqdk_wpc3": 1,
-        "dqdk_exact": 1, "cache_order": -1}
+        "dqdk_exact": 1, "cache_order": -1, "stream_policy": -1}
 wl = bench.PlanesWorkload(lib, B, C, H, W, dev, 1234)
 ref = None
 graph_ms = {}                              # set -> graph-replay ms per round
@@ -90,11 +104,15 @@ for rnd in range(ROUNDS):                  # (two rounds by default: the order o
             lib.set_option("planes_overlap", -1)
 for k, v in BASE.items():
     lib.set_option(k, v)
-if "order-0" in graph_ms:
-    base = graph_ms["order-0"]
-    print("== cache_order: graph-replay ms per round; noise = the larger of the set's and order-0's spread over the rounds")
+for option, zero in (("cache_order", "order-0"), ("stream_policy", "policy-0")):
+    if zero not in graph_ms:
+        continue
+    base = graph_ms[zero]
+    print(f"== {option}: graph-replay ms per round; noise = the larger of the set's and {zero}'s spread over the rounds")
     for name, v in graph_ms.items():
+        if not name.startswith(zero.split("-")[0] + "-"):
+            continue
         gain, noise = sum(base) / len(base) - sum(v) / len(v), max(max(v) - min(v), max(base) - min(base))
         below = all(a < b for a, b in zip(v, base))
-        print(f"   {name:20s} " + " ".join(f"{x:.4f}" for x in v) + f"  mean {sum(v) / len(v):.4f}  gain over order-0 {gain * 1e3:+6.1f} us  noise {noise * 1e3:4.1f} us"
-              f"  below order-0 in every round: {below}  wins: {name != 'order-0' and below and gain > noise}")
+        print(f"   {name:20s} " + " ".join(f"{x:.4f}" for x in v) + f"  mean {sum(v) / len(v):.4f}  gain over {zero} {gain * 1e3:+6.1f} us  noise {noise * 1e3:4.1f} us"
+              f"  below {zero} in every round: {below}  wins: {name != zero and below and gain > noise}")
