@@ -7,6 +7,7 @@ device library; the first kernel call does, and fails loudly if it has not been 
 """
 from . import augment, celovasz
 from .abn import ABN, InPlaceABN, InPlaceABNSync, convert_abn
+from .abncl import ABNChannelsLastFunction
 from .augment import (CITYSCAPES_ID_TO_TRAINID, AugmentParams, CSDataSet, DeviceAugment, DevicePrefetcher, VOCDataSet,
                       draw_params)
 from .celovasz import UpsampledCELovasz, UpsampledCELovaszFunction
@@ -28,5 +29,6 @@ __all__ = ["CrissCrossAttention", "CrissCrossFunction", "CA_Weight", "CA_Map", "
            "UpsampledCrossEntropyFunction", "UpsampledOhemCrossEntropy2d", "UpsampledOhemFunction",
            "celovasz", "UpsampledCELovasz", "UpsampledCELovaszFunction", "augment", "DeviceAugment", "DevicePrefetcher",
            "CSDataSet", "VOCDataSet", "AugmentParams", "draw_params", "CITYSCAPES_ID_TO_TRAINID", "DeviceSGD", "poly_schedule",
-           "DeviceMixedSGD", "bf16_parameters", "conv3x3", "DeviceConv3x3", "convert_conv3x3"]
+           "DeviceMixedSGD", "bf16_parameters", "conv3x3", "DeviceConv3x3", "convert_conv3x3",
+           "ABNChannelsLastFunction"]
 __version__ = "0.1.0"

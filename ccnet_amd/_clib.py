@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the fourteen C-ABI libraries share: the header scan, loading, prototypes, the version check, errors.
+"""What the ctypes bindings of the fifteen C-ABI libraries share: the header scan, loading, prototypes, the version check, errors.
 
 Each ``_x_lib.py`` keeps its constants, its ``_PROTOTYPES`` table and a :class:`CLibrary` subclass that names what differs.
 There is deliberately NO fallback: a missing library raises.  ``import torch`` must precede the ``CDLL`` of a device library

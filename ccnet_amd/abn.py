@@ -15,6 +15,10 @@ pass, and in backward one reduction and one apply pass.  Two arithmetics, one pe
 ``InPlaceABNSync`` reduces its training statistics over the ranks of the default process group: every rank's per-channel
 (count, mean, M2) is exchanged and merged in rank order with Chan's formula, and backward exchanges the two per-channel sums
 the same way.  There is no CPU fallback.
+
+Layers converted with ``convert_abn(model, mode, channels_last=True)`` hand a dense ``torch.channels_last`` input to
+:class:`ccnet_amd.abncl.ABNChannelsLastFunction` (libccnet_abncl.so, the same arithmetic on pixel-major rows) as it lies and
+return channels_last; every other input, and every layer without the attribute, runs as described above.
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ import torch.distributed as dist
 import inplace_abn
 
 from . import _abn_lib as L
+from . import abncl as _cl
 
 __all__ = ["ABN", "InPlaceABN", "InPlaceABNSync", "ABNFunction", "convert_abn"]
 
@@ -137,6 +142,7 @@ class _DeviceABN:
 
     inplace = False
     sync = False
+    channels_last = False      # convert_abn(..., channels_last=True): dense channels_last inputs run on libccnet_abncl.so
 
     @property
     def fused_epilogues(self):
@@ -168,13 +174,18 @@ class _DeviceABN:
         fused epilogues pass 'relu')."""
         activation = self.activation if activation is None else activation
         self._check(x, activation)
-        if self.inplace and not x.is_contiguous():
-            raise ValueError("in-place ABN needs a contiguous NCHW input")
-        x = x.contiguous()
+        # a dense channels_last input that is not NCHW-contiguous as well (C = 1 and H * W = 1 tensors are both, and stay on
+        # the NCHW kernels) goes to the pixel-major kernels as it lies
+        pixel_major = self.channels_last and _cl.is_dense_channels_last(x) and not x.is_contiguous()
+        if self.inplace and not pixel_major and not x.is_contiguous():
+            raise ValueError("in-place ABN needs a contiguous NCHW or a dense channels_last input" if self.channels_last
+                             else "in-place ABN needs a contiguous NCHW input")
+        if not pixel_major:
+            x = x.contiguous()
         if residual is not None:
             if residual.shape != x.shape:
                 raise ValueError(f"ABN: residual {tuple(residual.shape)} does not match the input {tuple(x.shape)}")
-            residual = residual.to(x.dtype).contiguous()
+            residual = _cl._dense(residual, x.dtype) if pixel_major else residual.to(x.dtype).contiguous()
         training = self.training
         if training and x.numel() // x.shape[1] <= 1:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
@@ -183,7 +194,8 @@ class _DeviceABN:
             group = dist.group.WORLD
         param = float(self.activation_param) if activation in (inplace_abn.ACT_LEAKY_RELU, inplace_abn.ACT_ELU) else 0.0
         cfg = (training, float(self.momentum), float(self.eps), L.ACTIVATIONS[activation], param, self.inplace, group)
-        return ABNFunction.apply(x, self.weight, self.bias, self.running_mean, self.running_var, residual, cfg)
+        function = _cl.ABNChannelsLastFunction if pixel_major else ABNFunction
+        return function.apply(x, self.weight, self.bias, self.running_mean, self.running_var, residual, cfg)
 
     def extra_repr(self):
         return super().extra_repr() + f", inplace={self.inplace}, device=True"
@@ -210,11 +222,12 @@ _TWINS = {inplace_abn.ABN: ABN, inplace_abn.InPlaceABN: InPlaceABN, inplace_abn.
           ABN: ABN, InPlaceABN: InPlaceABN, InPlaceABNSync: InPlaceABNSync}
 
 
-def convert_abn(model, mode):
+def convert_abn(model, mode, channels_last=False):
     """Swap every ``inplace_abn`` module of ``model`` (in place, returned) for its device twin, keeping the parameter and
     buffer tensors themselves (an optimiser built before stays valid).  ``mode``: 'device' (out-of-place arithmetic, what
-    the stock layer computes) or 'inplace' (the output overwrites the input, gamma = |weight| + eps).  Converting again
-    switches the mode."""
+    the stock layer computes) or 'inplace' (the output overwrites the input, gamma = |weight| + eps).  ``channels_last``:
+    the layers take a dense channels_last input as it lies and return channels_last (libccnet_abncl.so, no layout copy);
+    every other input, and every input when it is false, runs on the NCHW kernels.  Converting again switches the mode."""
     if mode not in ("device", "inplace"):
         raise ValueError(f"convert_abn: mode must be 'device' or 'inplace', not {mode!r}")
     inplace = mode == "inplace"
@@ -230,6 +243,7 @@ def convert_abn(model, mode):
                 new.weight, new.bias = m.weight, m.bias
             new.running_mean, new.running_var = m.running_mean, m.running_var
             new.inplace = inplace
+            new.channels_last = bool(channels_last)
             new.train(m.training)
             setattr(parent, name, new)
     return model

@@ -28,7 +28,9 @@ the same training step on random data, one process per GPU:
     convs      --device-conv3: every eligible 3x3 convolution (stride 1, padding == dilation) swapped for the library's implicit
                GEMM (ccnet_amd.conv3.convert_conv3x3), the images -- and with the stock optimiser the model -- in
                torch.channels_last (DeviceSGD and DeviceMixedSGD walk contiguous parameters: there the activations alone
-               carry the format); needs --bf16 or --bf16-params; refused with --abn device|inplace (NCHW-only layers) and --cpu
+               carry the format); needs --bf16 or --bf16-params; refused with --cpu, and with --abn device|inplace
+               (NCHW-only layers) unless --abn-channels-last puts those layers on their pixel-major kernels
+               (ccnet_amd.abncl: no layout copy between a converted convolution and its normalisation layer)
     parallel   DistributedDataParallel over RCCL (backend "nccl"), SyncBN statistics engine.py:52-57,75
                per-rank seed = rank                                                  train.py:154-155
 
@@ -153,14 +155,19 @@ def run(args, model_factory=None, quiet=False):
     else:
         model = model_factory()
     abn_mode = getattr(args, "abn", None)
+    abn_channels_last = getattr(args, "abn_channels_last", False)
     if abn_mode in ("device", "inplace"):
         from .abn import convert_abn
-        convert_abn(model, abn_mode)
+        # (--abn-channels-last: the layers take the converted convolutions' channels_last activations as they lie, and
+        # native_batch_norm_for_bf16_channels_last below finds no stock layer left to swap)
+        convert_abn(model, abn_mode, channels_last=abn_channels_last)
     device_conv3 = getattr(args, "device_conv3", False)
     if device_conv3:
         if not use_cuda:
             raise RuntimeError("--device-conv3 needs a HIP device (ccnet_amd has no CPU fallback for the convolution kernels)")
+        from . import conv3 as conv3_module
         from .conv3 import convert_conv3x3, native_batch_norm_for_bf16_channels_last
+        copies_before = conv3_module.layout_copies
         converted = convert_conv3x3(model)
         # (the stock normalisation layers now see bf16 channels_last activations: conv3.NativeChannelsLast says what that needs)
         native_batch_norm_for_bf16_channels_last(model)
@@ -291,10 +298,13 @@ def run(args, model_factory=None, quiet=False):
         if device_conv3:
             result["config"]["conv3"] = "device"
             result["config"]["conv3_layers"] = converted
+            result["layout_copies"] = conv3_module.layout_copies - copies_before
         if source is not None:
             result["data"] = "synthetic uint8 %d x %d frames through DeviceAugment" % source.frame
         if abn_mode is not None:
             result["abn"] = abn_mode
+            if abn_channels_last:
+                result["abn_channels_last"] = True
             result["step_losses"] = [round(float(v.float().item()), 6) for v in losses]
             if use_cuda:
                 result["max_memory_allocated_mb"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
@@ -367,7 +377,11 @@ def build_parser():
                     help="every eligible 3x3 convolution (stride 1, padding == dilation, groups 1, channel counts divisible by 8) "
                          "on the library's implicit-GEMM kernels (ccnet_amd.conv3.convert_conv3x3), the images (and, with the stock "
                          "optimiser, the model) in torch.channels_last; needs --bf16 or --bf16-params; refused with --abn device|inplace, whose layers are "
-                         "NCHW-only, and with --cpu; the JSON line then reports config.conv3 device")
+                         "NCHW-only (unless --abn-channels-last is given), and with --cpu; the JSON line then reports config.conv3 device")
+    ap.add_argument("--abn-channels-last", action="store_true",
+                    help="with --abn device|inplace and --device-conv3: the device ABN layers on their pixel-major kernels "
+                         "(ccnet_amd.abncl), which take the converted convolutions' channels_last activations with no layout "
+                         "copy; the JSON line then reports abn_channels_last true")
     ap.add_argument("--ohem-thres", type=float, default=0.6, help="OHEM probability threshold (train.py: 0.6)")
     ap.add_argument("--ohem-keep", type=int, default=200000, help="OHEM minimum kept pixels (train.py: 200000)")
     ap.add_argument("--cpu", action="store_true", help="tests only: gloo on CPU with an injected model")
@@ -389,10 +403,17 @@ def check_args(args):
         if getattr(args, "cpu", False):
             raise ValueError("--bf16-params cannot be combined with --cpu: it needs a HIP device (ccnet_amd has no CPU fallback "
                              "for the optimiser kernels)")
+    if getattr(args, "abn_channels_last", False):
+        if getattr(args, "abn", None) not in ("device", "inplace"):
+            raise ValueError("--abn-channels-last needs --abn device or --abn inplace: it selects the device ABN layers' "
+                             "channels_last kernels")
+        if not getattr(args, "device_conv3", False):
+            raise ValueError("--abn-channels-last needs --device-conv3: only the converted convolutions put the activations "
+                             "in channels_last")
     if getattr(args, "device_conv3", False):
         if not (getattr(args, "bf16", False) or getattr(args, "bf16_params", False)):
             raise ValueError("--device-conv3 needs --bf16 or --bf16-params: the convolution kernels take bf16 activations")
-        if getattr(args, "abn", None) in ("device", "inplace"):
+        if getattr(args, "abn", None) in ("device", "inplace") and not getattr(args, "abn_channels_last", False):
             raise ValueError("--device-conv3 cannot be combined with --abn device|inplace: the device ABN layers are NCHW-only, "
                              "the convolution kernels channels_last")
         if getattr(args, "cpu", False):
