@@ -12,7 +12,8 @@
 //                Neither the up-sampled tiles nor the per-scale (Hs, Ws) map is materialised.
 //
 // A tap whose weight is exactly 0 is not read, so at Hs == H, Ws == W the accumulate kernel evaluates one position a pixel
-// and gives sliding_kernel's score bit for bit, and the tiles kernel copies.
+// and gives sliding_kernel's score bit for bit, and the tiles kernel copies.  That rule is the resample's (axis_tap's taps);
+// inside a tile, sample() of eval_sample.hpp sums its four terms unconditionally, as PyTorch does.
 #pragma once
 #include "eval_sample.hpp"
 
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const float *tiles
             float s = score_in ? score_in[at] + r : r;
             if (divide_by > 0) s /= (float)divide_by;
             if (score_out) score_out[at] = s;
-            if (c == 0 || s > best) {                 // the first maximum, as np.argmax
+            if (c == 0 || s > best || (s != s && best == best)) {   // the first maximum, as np.argmax: a NaN is one
                 best = s;
                 arg = c;
             }

@@ -17,10 +17,18 @@
  *      flip the same tiles of the scaled image mirrored along W: column xs of the flipped frame is column Ws - 1 - xs.
  *   4. per-scale score S_s on (Hs, Ws): exactly steps 1-2 of ccnet_eval.h (PyTorch's align_corners=True fp32 arithmetic
  *      inside a tile, fp32 sum in tile order over the count, 0.5 * (plain + flipped) with the flipped pass mirrored back along W).
+ *      The zero-weight rule of steps 2 and 5 does NOT hold inside a tile: as in PyTorch, the bilinear sample is the
+ *      unconditional sum of its four terms, so a non-finite logit makes S_s non-finite at every position of its tile whose
+ *      four neighbours include it, as NaN (0 * inf) where its weight is 0.  Steps 2 and 5 then carry such a position to exactly
+ *      the outputs with a non-zero tap weight on it.
  *   5. back to (H, W): R_s = the resample of step 2 from (Hs, Ws) to (H, W), i.e. ndimage.zoom by (H / Hs, W / Ws).  For
  *      Hs == H and Ws == W every weight is exactly 0 or 1 and R_s == S_s bit for bit.
  *   6. combine: score = (sum over s of R_s) / S, summed in fp32 in call order with one fp32 divide at the end; pred = the
  *      first maximum; confusion[label][pred] += 1 when label != ignore_label and 0 <= label < C (ccnet_eval.h steps 3-4).
+ *      "First maximum" is np.argmax's: among equal scores the lowest class, and a NaN score counts as the maximum (the first
+ *      NaN wins).  The kernel used to skip NaN scores (`s > best` alone); np.argmax is the reference's, so the kernel follows it.
+ *      For scores without a NaN nothing changes.  (ccnet_eval_sliding_f32 still compares with `s > best` alone, so the two
+ *      libraries' predictions can differ where a score is NaN, and only there.)
  * The divergences of ccnet_eval.h carry over: each image its own tiles, un-flip along W, at least one tile per axis.
  *
  * ccnet_mseval_tiles_f32 is steps 2-3 in one gather kernel: entries [first, first + count) of each image's sequence of T

@@ -5,7 +5,8 @@ import numpy as np
 
 GUARD = 64                                   # guard elements on each side of every buffer
 _KINDS = {"f32": (4, np.uint32, 0xCDCDCDCD), "bf16": (2, np.uint16, 0xCDCD),
-          "f64": (8, np.uint64, 0x7FF8000000000000)}        # fp64 bands hold NaN
+          "f64": (8, np.uint64, 0x7FF8000000000000),        # fp64 bands hold NaN
+          "u8": (1, np.uint8, 0xCD), "i64": (8, np.uint64, 0xCDCDCDCDCDCDCDCD)}
 
 
 class HostMemory:

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import eval_oracle as O
+import mseval_cases as MC
 import mseval_oracle as M
 from conftest import GOLDEN
 
@@ -232,6 +233,73 @@ def test_evaluator_is_the_chain_of_the_two_entry_points_and_tile_batch_does_not_
     assert np.all(O.top2_gap(ref)[diff] < tol)
     ev.reset()
     assert int(ev.confusion.sum()) == 0
+
+
+def test_tile_batch_that_cuts_a_chunk_across_the_plain_and_flipped_tiles():
+    """scale 0.75 of 128 x 256 has T + T_flip = 2 * 3 entries: tile_batch = 5 asks for [0, 5), which starts in the plain tiles and
+    ends in the flipped ones, and leaves [5, 6)"""
+    from ccnet_amd import MultiScaleEvaluator
+    H, W, C, scales = 128, 256, 19, (0.75, 1.0, 1.5)
+    net = O.make_toy_net(C, 7).to(DEV)
+    image_np, label_np = O.make_case_inputs(1, H, W, C, seed=7)
+    image, label = dev(image_np), dev(label_np)
+    out = {}
+    for tile_batch in (8, 5):
+        ev = MultiScaleEvaluator(C, scales=scales, tile_size=(97, 97), flip=True, tile_batch=tile_batch)
+        geo = ev.geometry(H, W)
+        assert 2 * len(geo[0][2]) == 6
+        logits = ev.net_logits(net, image)
+        pred = ev.accumulate(logits, label, H, W)
+        torch.cuda.synchronize()
+        np_logits = [lg.cpu().numpy().reshape(1, -1, C, lg.shape[2], lg.shape[3]) for lg in logits]
+        out[tile_batch] = np_logits, M.multiscale_scores(np_logits, geo, H, W, True), pred.cpu().numpy()
+    tol = 1e-5 * max(float(np.abs(lg).max()) for lg in out[8][0])
+    err = max(float(np.abs(a - b).max()) for a, b in zip(out[5][0], out[8][0]))
+    diff = out[5][2] != out[8][2]
+    print(f"tile_batch 5 against 8: logits differ by {err:.3e} (bar {tol:.3e}), predictions at {int(diff.sum())} pixels")
+    assert err <= tol and np.abs(out[5][1] - out[8][1]).max() <= tol
+    assert np.all(O.top2_gap(out[8][1])[diff] < tol)
+
+
+def test_argument_validation_of_the_two_calls_raises():
+    from ccnet_amd.evaluate import accumulate_call, scaled_tiles_call
+    N, C, H, W = 1, 5, 30, 40
+    Hs, Ws, origins, tile = M.geometry(H, W, 0.5, (33, 33), False)
+    logits = torch.zeros((N * len(origins), C, 5, 5), device=DEV)
+    call = lambda **kw: accumulate_call(logits, origins, False, N, tile, Hs, Ws, H, W, **kw)       # noqa: E731
+    call(score_out=torch.empty((N, C, H, W), device=DEV))                                          # the well-formed call passes
+    with pytest.raises(RuntimeError, match="score_out must be a contiguous"):
+        call(score_out=torch.empty((N, C, W, H), device=DEV).transpose(2, 3))                      # the right shape, strided
+    with pytest.raises(RuntimeError, match="labels must be a contiguous torch.int64"):
+        call(labels=torch.zeros((N, H, W), dtype=torch.int32, device=DEV), pred=torch.empty((N, H, W), dtype=torch.uint8,
+                                                                                             device=DEV))
+    with pytest.raises(RuntimeError, match="score_out must be a contiguous"):
+        call(score_out=torch.empty((N, C, H, W + 1), device=DEV))
+    with pytest.raises(RuntimeError, match="pred must be a contiguous"):
+        call(pred=torch.empty((N, H, W), dtype=torch.int64, device=DEV))
+    image = torch.zeros((N, 3, H, W), device=DEV)
+    scaled_tiles_call(image, Hs, Ws, origins, tile, False, out=torch.empty((N, len(origins), 3) + tile, device=DEV))
+    with pytest.raises(RuntimeError, match="out must be a contiguous fp32 tensor of shape"):
+        scaled_tiles_call(image, Hs, Ws, origins, tile, False, out=torch.empty((N, len(origins) + 1, 3) + tile, device=DEV))
+    with pytest.raises(RuntimeError, match="out must be a contiguous fp32 tensor of shape"):
+        scaled_tiles_call(image, Hs, Ws, origins, tile, False,
+                          out=torch.empty((N, len(origins), 3, tile[1], tile[0]), device=DEV).transpose(3, 4))
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the library at its limits, over the C ABI on guarded device buffers (tests/mseval_cases.py; the emulator runs the same table)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def guarded():
+    from ccnet_amd import _mseval_lib
+    yield _mseval_lib.get_lib(), MC.DeviceMemory()
+    print("largest error / bar on the device:", {k: round(v, 4) for k, v in MC.WORST.items()})
+
+
+@pytest.mark.parametrize("name", MC.ALL)
+def test_limits_on_guarded_buffers(guarded, name):
+    MC.run_case(name, *guarded)
 
 
 def stock_chain(logits, geo, N, H, W, flip):

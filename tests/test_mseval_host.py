@@ -11,6 +11,7 @@ import torch
 
 import eval_oracle as O
 import lib_checks as L
+import mseval_cases as MC
 import mseval_oracle as M
 from conftest import GOLDEN, ROOT
 
@@ -346,3 +347,11 @@ def test_emulated_in_place_accumulation_and_divide_by(emu):
     np.testing.assert_array_equal(conf, 2 * O.confusion(label, pred, C))        # accumulated over the two calls
     undivided, _, _ = emu_accumulate(emu, logits[1], geo[1], H, W, True, score_in=first)
     assert np.array_equal(out, undivided / np.float32(2)) and not np.array_equal(out, undivided)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the library at its limits, over the C ABI on guarded host buffers (tests/mseval_cases.py; the device runs the same table)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MC.ALL)
+def test_emulated_limits(emu, name):
+    MC.run_case(name, emu, MC.HostMemory())
