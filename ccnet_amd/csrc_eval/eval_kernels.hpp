@@ -43,7 +43,7 @@ __global__ __launch_bounds__(kThreads) void sliding_kernel(const float *tiles, T
             float s = pass_mean(img, g, G, 0, c, y, x, cnt);
             if (G.T_flip) s = 0.5f * (s + pass_mean(img, g, G, G.T, c, y, xf, cntf));
             if (probs) probs[((size_t)n * C + c) * HW + i] = s;
-            if (c == 0 || s > best) {                 // the first maximum, as np.argmax
+            if (first_maximum(c, s, best)) {          // as np.argmax: a NaN is one
                 best = s;
                 arg = c;
             }

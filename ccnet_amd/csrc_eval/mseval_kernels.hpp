@@ -20,6 +20,7 @@
 namespace mseval {
 
 using segeval::covers;
+using segeval::first_maximum;
 using segeval::Geometry;
 using segeval::global_add;
 using segeval::kPixPerBlock;
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const float *tiles
             float s = score_in ? score_in[at] + r : r;
             if (divide_by > 0) s /= (float)divide_by;
             if (score_out) score_out[at] = s;
-            if (c == 0 || s > best || (s != s && best == best)) {   // the first maximum, as np.argmax: a NaN is one
+            if (first_maximum(c, s, best)) {          // as np.argmax: a NaN is one
                 best = s;
                 arg = c;
             }

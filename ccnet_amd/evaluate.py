@@ -74,13 +74,26 @@ def run_net(net, tiles: torch.Tensor) -> torch.Tensor:
 
 def sliding_call(logits, origins, flip, N, tile_size, H, W, labels=None, ignore_label=255, probs=None, pred=None,
                  confusion=None):
-    """One ccnet_eval_sliding_f32 launch on the current stream.  ``logits`` (N * (T + T_flip), C, h, w) fp32."""
+    """One ccnet_eval_sliding_f32 launch on the current stream.  ``logits`` (N * (T + T_flip), C, h, w) fp32, ``labels``
+    (N, H, W) int64, ``probs`` (N, C, H, W) fp32, ``pred`` (N, H, W) uint8, ``confusion`` (C, C) int64 (it needs labels), all
+    contiguous: anything else raises before the launch, nothing is converted or copied."""
     _require_device(logits, labels, probs, pred, confusion)
     lib = _eval_lib.get_lib()
     T = len(origins)
     if T > _eval_lib.MAX_TILES:
         raise RuntimeError(f"ccnet_amd.evaluate: {T} tiles, the kernel takes at most {_eval_lib.MAX_TILES}")
+    if logits.dim() != 4:
+        raise RuntimeError(f"ccnet_amd.evaluate: logits must be a 4-d (N * tiles, C, h, w) tensor, got {tuple(logits.shape)}")
     C, h, w = logits.shape[1:]
+    want = {"logits": (logits, (N * T * (2 if flip else 1), C, h, w), torch.float32),
+            "labels": (labels, (N, H, W), torch.int64), "probs": (probs, (N, C, H, W), torch.float32),
+            "pred": (pred, (N, H, W), torch.uint8), "confusion": (confusion, (C, C), torch.int64)}
+    for name, (t, shape, dtype) in want.items():                          # the kernel indexes raw pointers by these shapes
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise RuntimeError(f"ccnet_amd.evaluate: {name} must be a contiguous {dtype} tensor of shape {shape}, "
+                               f"got {t.dtype} {tuple(t.shape)}" + ("" if t.is_contiguous() else ", not contiguous"))
+    if confusion is not None and labels is None:
+        raise RuntimeError("ccnet_amd.evaluate: confusion needs labels")
     y1x1 = _eval_lib.origins_array(origins)
     ptr = lambda t: None if t is None else t.data_ptr()                  # noqa: E731
     lib.check(lib.ccnet_eval_sliding_f32(logits.data_ptr(), T, T if flip else 0, y1x1, N, C, h, w, int(tile_size[0]),
@@ -173,7 +186,9 @@ class SegEvaluator:
 
     @torch.no_grad()
     def accumulate(self, logits, label, H, W):
-        """pred and confusion counts from net_logits' output; returns the uint8 (N, H, W) prediction."""
+        """pred and confusion counts from net_logits' output; returns the uint8 (N, H, W) prediction.  ``logits`` must be what
+        net_logits returns, contiguous fp32 (N * (T + T_flip), C, h, w): a channels_last or sliced tensor raises, as in
+        MultiScaleEvaluator."""
         _require_device(logits, label, self.confusion)
         if logits.shape[1] != self.num_classes:
             raise RuntimeError(f"SegEvaluator: the net gives {logits.shape[1]} classes, {self.num_classes} expected")

@@ -11,9 +11,18 @@
  *      cropped, pad_image, evaluate.py:95-100); the samples are summed in fp32 in tile order and divided by their count;
  *      the flipped pass works in the flipped frame: original column x is its column W - 1 - x;
  *   2. with a flipped pass the score is 0.5 * (plain + flipped);
- *   3. pred = the first maximum over the C scores (np.argmax's tie rule);
+ *   3. pred = the first maximum over the C scores, as np.argmax: among equal scores the lowest class, and a NaN score counts
+ *      as the maximum (the first NaN wins).  NaN scores are reachable from a +inf logit: the bilinear sample of step 1 is
+ *      PyTorch's unconditional sum of its four terms, so the logit makes the score +inf at the positions of its tile with a
+ *      non-zero weight on it and NaN (0 * inf) at those of its four-neighbour footprint with weight 0.  The rule is one
+ *      function (first_maximum, eval_sample.hpp) shared with ccnet_mseval_accumulate_f32;
  *   4. confusion[label][pred] += 1 when label != ignore_label and 0 <= label < C.
  * Whole-image evaluation (predict_whole) is the same call with T = 1, origin (0, 0) and tile = image.
+ *
+ * The call checks that every tile origin lies inside the image, not that the tiles cover it.  A pixel that no tile covers in
+ * one of the passes has a count of 0 there and gets 0 / 0: its score is NaN for every class (the other pass's half does not
+ * change that), pred = 0 by the rule of step 3, and it is counted at confusion[label][0].  Nothing outside the outputs is
+ * read or written for it.  The emulator build and the device agree on this.
  *
  * Deliberate divergences from the reference: every image of a batch gets its own tiles (the reference adds tile 0's
  * prediction to every image of the batch); the flipped pass is mirrored back along W, the axis that was flipped (the

@@ -27,8 +27,8 @@
  *      first maximum; confusion[label][pred] += 1 when label != ignore_label and 0 <= label < C (ccnet_eval.h steps 3-4).
  *      "First maximum" is np.argmax's: among equal scores the lowest class, and a NaN score counts as the maximum (the first
  *      NaN wins).  The kernel used to skip NaN scores (`s > best` alone); np.argmax is the reference's, so the kernel follows it.
- *      For scores without a NaN nothing changes.  (ccnet_eval_sliding_f32 still compares with `s > best` alone, so the two
- *      libraries' predictions can differ where a score is NaN, and only there.)
+ *      For scores without a NaN nothing changes.  ccnet_eval_sliding_f32 takes its prediction from the same function
+ *      (first_maximum, eval_sample.hpp).
  * The divergences of ccnet_eval.h carry over: each image its own tiles, un-flip along W, at least one tile per axis.
  *
  * ccnet_mseval_tiles_f32 is steps 2-3 in one gather kernel: entries [first, first + count) of each image's sequence of T

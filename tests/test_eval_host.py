@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import lib_checks as L
+import eval_cases as EC
 import eval_oracle as O
 from conftest import GOLDEN, ROOT
 
@@ -274,6 +275,24 @@ def test_emulated_degenerate_geometry(emu, H, W, tile, hw, flip):
     diff = pred != O.argmax(ref)
     assert np.all(O.top2_gap(ref)[diff] < 1e-5 * np.abs(tiles).max())
     np.testing.assert_array_equal(conf, O.confusion(label, pred, 7))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the library at its limits, over the C ABI on guarded host buffers (tests/eval_cases.py; the device runs the same table).
+# Every call is repeated through the multi-scale library at Hs = H, Ws = W, hence its emulator build.
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def emu_multi():
+    from ccnet_amd._mseval_lib import MsEvalLibrary
+    emu_dir = os.path.join(ROOT, "tests", "emu_eval")
+    out = L.build_emu_library(os.path.join(emu_dir, "libmseval_emu.so"), os.path.join(EVAL_CSRC, "mseval_api.hip"),
+                              [emu_dir, L.EMU_DIR, EVAL_CSRC, L.INCLUDE], reads=(L.EMU_COMMON_DIR, L.COMMON_CSRC))
+    return MsEvalLibrary(out)
+
+
+@pytest.mark.parametrize("name", EC.ALL)
+def test_emulated_limits(emu, emu_multi, name):
+    EC.run_case(name, emu, emu_multi, EC.HostMemory())
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import eval_cases as EC
 import eval_oracle as O
 from conftest import GOLDEN, ROOT
 
@@ -288,6 +289,89 @@ def test_no_host_sync_in_the_post_processing():
         torch.cuda.set_sync_debug_mode(0)
     torch.cuda.synchronize()
     assert pred.shape == (1, 300, 400) and int(ev.confusion.sum()) == 2 * 300 * 400
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the library at its limits, over the C ABI on guarded device buffers (tests/eval_cases.py; the emulator runs the same table).
+# Every call is repeated through libccnet_mseval.so at Hs = H, Ws = W: the same bits, predictions and counts.
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def guarded():
+    from ccnet_amd import _eval_lib, _mseval_lib
+    yield _eval_lib.get_lib(), _mseval_lib.get_lib(), EC.DeviceMemory()
+    print("largest error / bar on the device:", {k: round(v, 4) for k, v in EC.WORST.items()})
+
+
+@pytest.mark.parametrize("name", EC.ALL)
+def test_limits_on_guarded_buffers(guarded, name):
+    EC.run_case(name, *guarded)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sliding_call hands raw pointers to a kernel that indexes them by the shapes it is told: it refuses every other tensor
+# ---------------------------------------------------------------------------------------------------------------------
+def _validation_inputs():
+    from ccnet_amd.evaluate import tile_grid
+    N, C, H, W, tile = 2, 5, 12, 20, (8, 8)
+    origins = tile_grid(H, W, tile)
+    logits = torch.from_numpy(EC.rand_logits(N, len(origins), C, (2, 2), False, 500)).to(DEV).flatten(0, 1)
+    labels = torch.from_numpy(O.make_case_inputs(N, H, W, C, seed=501)[1]).to(DEV)
+    return N, C, H, W, tile, origins, logits, labels
+
+
+def test_sliding_call_refuses_tensors_the_kernel_would_misread():
+    from ccnet_amd.evaluate import sliding_call
+    N, C, H, W, tile, origins, logits, labels = _validation_inputs()
+    probs = torch.full((N, C, H, W), float("nan"), device=DEV)
+    pred = torch.full((N, H, W), 0xEE, dtype=torch.uint8, device=DEV)
+    conf = torch.full((C, C), 7, dtype=torch.int64, device=DEV)
+    wide = torch.full((N, H, W + 4), 0xEE, dtype=torch.uint8, device=DEV)
+    last = torch.full((N, C, H, W), float("nan"), device=DEV).contiguous(memory_format=torch.channels_last)
+    flat = torch.full((C * C,), 7, dtype=torch.int64, device=DEV)
+    assert not last.is_contiguous() and not wide[:, :, :W].is_contiguous() and logits[:-1].is_contiguous()
+    call = lambda lg=logits, **kw: sliding_call(lg, origins, False, N, tile, H, W, **kw)           # noqa: E731
+    for match, kw in (
+            ("probs must be a contiguous", dict(probs=last)),                                      # channels_last
+            ("pred must be a contiguous", dict(pred=wide[:, :, :W])),                              # a column slice
+            ("labels must be a contiguous torch.int64", dict(labels=labels.to(torch.int32), pred=pred, confusion=conf)),
+            ("logits must be a contiguous", dict(lg=logits[:-1], probs=probs, pred=pred)),         # one tile short
+            ("logits must be a contiguous", dict(lg=logits.to(torch.float64), probs=probs)),
+            ("confusion must be a contiguous", dict(labels=labels, pred=pred, confusion=flat)),    # C * C, but not (C, C)
+            ("pred must be a contiguous", dict(pred=pred.to(torch.int64))),
+            ("probs must be a contiguous", dict(probs=probs[:1])),
+            ("confusion needs labels", dict(pred=pred, confusion=conf))):
+        with pytest.raises(RuntimeError, match=match):
+            call(**kw)
+    torch.cuda.synchronize()
+    # nothing was launched: every output still holds its prefill
+    assert torch.isnan(probs).all() and torch.isnan(last).all()
+    assert (pred == 0xEE).all() and (wide == 0xEE).all() and (conf == 7).all() and (flat == 7).all()
+    call(labels=labels, probs=probs, pred=pred, confusion=conf)                                    # the well-formed call passes
+    torch.cuda.synchronize()
+    assert not torch.isnan(probs).any() and (pred < C).all()
+    assert int((conf - 7).sum()) == int(((labels >= 0) & (labels < C)).sum())
+
+
+def test_evaluator_accumulate_refuses_strided_logits():
+    """SegEvaluator.accumulate is public and reaches the kernel with the caller's logits: channels_last or sliced ones raise (as
+    in MultiScaleEvaluator) instead of being read through the wrong strides, and the counts stay as they were"""
+    from ccnet_amd import SegEvaluator
+    N, C, H, W, tile, origins, logits, labels = _validation_inputs()
+    ev = SegEvaluator(C, tile_size=tile)
+    want = ev.accumulate(logits, labels, H, W)
+    counts = ev.confusion.clone()
+    padded = torch.zeros((logits.shape[0], C, 2, 3), device=DEV)
+    padded[..., :2] = logits
+    for strided in (logits.contiguous(memory_format=torch.channels_last), padded[..., :2]):
+        assert torch.equal(strided, logits) and not strided.is_contiguous()
+        with pytest.raises(RuntimeError, match="logits must be a contiguous"):
+            ev.accumulate(strided, labels, H, W)
+    with pytest.raises(RuntimeError, match="labels must be a contiguous"):
+        ev.accumulate(logits, labels[:, :, :W - 1], H, W)
+    torch.cuda.synchronize()
+    assert torch.equal(ev.confusion, counts)
+    assert torch.equal(ev.accumulate(logits.clone(), labels.to(torch.int32), H, W), want)         # labels are converted, as before
+    assert torch.equal(ev.confusion, 2 * counts)
 
 
 DRIVER = ["-m", "ccnet_amd.eval_synthetic", "--images", "4", "--height", "256", "--width", "512", "--tile", "193",
